@@ -13,9 +13,22 @@ resident in HBM when the timed region starts:
     infer : eval forward + decode (configs[1]-style)
 One process per GPU; W untimed warm-up steps, then EXACTLY K steps between barrier+synchronize
 pairs; time = MAX over ranks; rank 0 prints ONE JSON line.  `value` = frame pairs per second over
-all N GPUs (weak scaling: the per-GPU batch is fixed).
+all N GPUs (weak scaling: the per-GPU batch is fixed); `ms_per_step` = milliseconds of one timed step.
 
-Extra objects on the line:
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR) and print the line.
+--dump-outputs DIR: what the timed path returned in its LAST timed step, as DIR/<name>.npy (float32 / float64, rank 0):
+    train  : the loss dict (one file per entry), a fixed seeded sample of the parameter gradients (all parameters in
+             named_parameters() order, flattened and concatenated) with its flat indices, and the BatchNorm running statistics
+    infer  : the decoded output [B, A, 13] (above 32 MB: a fixed seeded sample of its rows, with the row indices)
+    stream : the detections that survive NMS (rows of det up to count), their anchor indices and the per-frame counts
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+--full adds everything else the benchmark measures, each leg with runs of its own (all null on a plain line):
+  host_issue   — host time to issue one step into empty queues (config.host_issue_ms_per_step).
+  parity       — the committed parity figures of the benchmarked dtype and configuration.
+  extras       — (--extras 1) the drop-in boundary, the 4-pair step, the other BASELINE configurations and the fp32 / fp16
+                 modes (train), the single-pass comparison of split-K (stream).
+Extra objects on a --full line:
   roofline     — dominant kernel (conv_igemm / conv_wgrad on the MFMA units): algorithmic conv FLOPs per
                  step (2*Cin*Cout*k^2*Ho*Wo, x3 for fwd+bwd) / the summed duration of
                  those kernels per step, measured live with HIP events on the launch stream.
@@ -80,6 +93,12 @@ def parse():
                     help="train: 'trainstep' = streamyolo_amd.TrainStep (sync-free fast path, gradients stay in the flat arena); "
                          "'dropin' = the UNCHANGED reference trainer's call sequence, model(inps, targets)['total_loss'].backward() "
                          "(exps/train_utils/double_trainer.py:107-114), through the autograd.Function of train_forward")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: roofline / per-kernel profile, host issue time, CPU baseline, "
+                         "parity record and the extras (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -264,7 +283,7 @@ def other_configs(args):
     }
     out = {}
     for name, extra in runs.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--extras", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--extras", "0",
                "--height", str(args.height), "--width", str(args.width)] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -342,8 +361,70 @@ class _Mark:
         return self.ev.elapsed_time(other.ev) if self.ev is not None else (other.t - self.t) * 1e3
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+GRAD_SAMPLE = 1 << 21            # gradient elements kept by --dump-outputs (values fp32 + flat indices fp64: 24 MB at most)
+
+
+def step_outputs(workload, model, out):
+    """What a caller of the timed path receives from one step, as {name: tensor} (see --dump-outputs in the module docstring)."""
+    if workload == "train":
+        arrays = {k: torch.as_tensor(v).detach().reshape(-1) for k, v in sorted(out.items())}
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                           for _, p in model.named_parameters()])
+        n = grads.numel()
+        if n > GRAD_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, n, (GRAD_SAMPLE,), generator=g).unique()        # sorted, fixed for a given parameter count
+        else:
+            idx = torch.arange(n)
+        arrays["grad_sample"] = grads[idx.to(grads.device)]
+        arrays["grad_sample_index"] = idx.double()
+        arrays["bn_running_stats"] = torch.cat([b.detach().reshape(-1).float() for name, b in model.named_buffers()
+                                                if name.endswith(("running_mean", "running_var"))])
+        return arrays
+    if workload == "stream":
+        det, anchor, count = out
+        counts = [int(c) for c in count.cpu()]
+        return {"detections": torch.cat([det[i, :c] for i, c in enumerate(counts)]),
+                "anchor_index": torch.cat([anchor[i, :c] for i, c in enumerate(counts)]).double(),
+                "count": torch.tensor(counts, dtype=torch.float64)}
+    rows = out.reshape(-1, out.shape[-1])
+    if rows.numel() * 4 <= DUMP_LIMIT_BYTES // 2:
+        return {"decoded": out}
+    g = torch.Generator().manual_seed(0)                         # large batches: a fixed sample of the [B * A] decoded rows
+    idx = torch.randint(0, rows.shape[0], (DUMP_LIMIT_BYTES // 2 // (4 * rows.shape[1]),), generator=g).unique()
+    return {"decoded_row_sample": rows[idx.to(rows.device)], "decoded_row_sample_index": idx.double()}
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy: float64 stays float64, everything else is written as float32."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t.double() if t.dtype == torch.float64 else t.float()).numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
+    if args.full and not os.environ.get("STREAMYOLO_TUNE_CACHE"):
+        # --full runs other configurations (here and in child processes) whose shapes the committed tuner cache may not hold:
+        # they tune into a copy of it, so the tracked streamyolo_amd/lib/tune_cache.json stays as it is
+        import atexit
+        import shutil
+        import tempfile
+        tune_dir = tempfile.mkdtemp(prefix="sy_bench_tune_")
+        src = os.path.join(ROOT, "streamyolo_amd", "lib", "tune_cache.json")
+        if os.path.exists(src):
+            shutil.copyfile(src, os.path.join(tune_dir, "tune_cache.json"))
+        os.environ["STREAMYOLO_TUNE_CACHE"] = os.path.join(tune_dir, "tune_cache.json")
+        atexit.register(shutil.rmtree, tune_dir, True)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)                                          # does not return
     rank = int(os.environ.get("RANK", "0"))
@@ -485,6 +566,7 @@ def main():
                     return plan.run_stream_taped(frame, post=post, check_params=False)
                 out = plan.run_stream(frame)
                 return post(out)
+        graph_out = None
         with torch.no_grad():
             plan.run_stream(frame, first=True)
         if args.graph == 1:
@@ -493,18 +575,18 @@ def main():
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                eager()
+                graph_out = eager()
 
         def step():
             if graph is not None:
                 graph.replay()
-            else:
-                eager()
+                return graph_out
+            return eager()
         profile = lambda n: plan.profile(frame, n)                          # noqa: E731
     else:
         model.eval()
         plan = model._plans.inference(model.backbone, model.head, "off_pipe", x, owner=model)
-        graph = None
+        graph = graph_out = None
 
         def eager():
             with torch.no_grad():
@@ -515,13 +597,13 @@ def main():
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                eager()
+                graph_out = eager()
 
         def step():
             if graph is not None:
                 graph.replay()
-            else:
-                eager()
+                return graph_out
+            return eager()
         profile = lambda n: plan.profile(x, n)                  # noqa: E731
 
     def barrier():
@@ -541,15 +623,18 @@ def main():
         marks = [_Mark(on_gpu) for _ in range(steps + 1)]
         t0 = time.perf_counter()
         marks[0].record()
+        out = None
         for i in range(steps):
-            fn()
+            out = fn()
             marks[i + 1].record()
         host = (time.perf_counter() - t0) / steps * 1e3          # launch-side time (the GPU runs behind it)
         barrier()
         el = time.perf_counter() - t0
-        return el, host, sorted(marks[i].ms_to(marks[i + 1]) for i in range(steps))
+        return el, host, sorted(marks[i].ms_to(marks[i + 1]) for i in range(steps)), out
 
-    elapsed, host_ms, per_step = timed(step, args.warmup, args.steps)
+    elapsed, host_ms, per_step, last_out = timed(step, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(workload, model, last_out))
     pct = lambda q: per_step[min(len(per_step) - 1, max(0, int(round(q * (len(per_step) - 1)))))]      # noqa: E731
     step_stats = {"median": round(pct(0.5), 4), "p10": round(pct(0.1), 4), "p90": round(pct(0.9), 4)}
     rank_ms = [elapsed / args.steps * 1e3]
@@ -584,13 +669,13 @@ def main():
         if on_gpu:
             torch.cuda.synchronize()
         return sorted(ts)[len(ts) // 2]
-    host_issue_ms = host_issue(step)
+    host_issue_ms = host_issue(step) if args.full else None
     launches = None
     if workload == "train" and args.path == "trainstep" and stepper.plan is not None and stepper.plan.programs:
         launches = sum(prog[1].size()[1] for prog in stepper.plan.programs.values())
 
     roofline = None
-    if rank == 0 and on_gpu:
+    if args.full and rank == 0 and on_gpu:
         dominant = None
         if workload == "train":
             rows = profile_rows(3)                              # [(kind, shape, launches, ms, flops)] per step
@@ -642,7 +727,7 @@ def main():
 
     # ---- beside the headline (1 GPU, default training path): the drop-in boundary and configs[3]'s per-GPU load ----------
     extras = None
-    if workload == "train" and world == 1 and args.extras and args.path == "trainstep" and not args.train_graph:
+    if args.full and workload == "train" and world == 1 and args.extras and args.path == "trainstep" and not args.train_graph:
         extras = {}
         ks, kw = max(5, args.steps // 2), 3
 
@@ -651,14 +736,14 @@ def main():
                 p_.grad = None
             out = model(x, (lab, sup))
             out["total_loss"].backward()
-        el, hst, _ = timed(dropin_step, kw, ks)
+        el, hst, _, _ = timed(dropin_step, kw, ks)
         extras["dropin"] = {"ms_per_step": el / ks * 1e3, "value": B * ks / el, "steps": ks, "host_issue_ms_per_step": round(host_issue(dropin_step), 3),
                             "what": "model(x, targets)['total_loss'].backward() — the unchanged trainer's call sequence "
                                     "(exps/train_utils/double_trainer.py:107-114) through train_forward's autograd.Function"}
         if B == 8 and not args.u8_input:
             x4, lab4, sup4 = x[:4].contiguous(), lab[:4].contiguous(), sup[:4].contiguous()
             st4 = TrainStep(model, world_size=1, process_group=None, graph=False)
-            el, hst, _ = timed(lambda: st4.step(x4, (lab4, sup4)), kw + 2, ks)
+            el, hst, _, _ = timed(lambda: st4.step(x4, (lab4, sup4)), kw + 2, ks)
             extras["per_gpu_batch_4"] = {"ms_per_step": el / ks * 1e3, "value": 4 * ks / el, "steps": ks,
                                          "host_issue_ms_per_step": round(host_issue(lambda: st4.step(x4, (lab4, sup4))), 3),
                                          "what": "same step at 4 frame pairs / GPU: BASELINE.json configs[3] (global batch 32 on 8 "
@@ -666,7 +751,7 @@ def main():
         if not EMU_SELFTEST and args.model == "l" and B == 8 and args.dtype == "bf16" and (args.height, args.width) == (600, 960):
             extras["other_configs"] = other_configs(args)
 
-    if workload == "stream" and world == 1 and args.extras and plan.allow_split_k:
+    if args.full and workload == "stream" and world == 1 and args.extras and plan.allow_split_k:
         # the same step with every layer on its single-pass kernel: what split-K buys at batch 1 (same process, same box)
         chosen = [(op.x.H, op.x.W, op.x.C, op.y.C) + tuple(op._tiles["splitk"]) for op in plan.ops
                   if op.kind == "conv" and op._tiles.get("splitk", (1,))[0] > 1]
@@ -682,9 +767,9 @@ def main():
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    eager()
+                    graph_out = eager()
             ks = max(20, args.steps // 2)
-            el, hst, _ = timed(step, 5, ks)
+            el, hst, _, _ = timed(step, 5, ks)
             extras["single_pass"] = {"ms_per_step": el / ks * 1e3, "steps": ks,
                                      "what": "same step, --split-k 0 (every 3x3 layer as one pass over its input channels)"}
             plan.allow_split_k = True
@@ -706,7 +791,7 @@ def main():
                 "rank_ms_per_step": [round(v, 4) for v in rank_ms]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU_SELFTEST:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU_SELFTEST:
         cpu = cpu_baseline(args, workload, flops_pair)
 
     if rank == 0:
@@ -735,11 +820,12 @@ def main():
                                           "%d of %d anchors pass conf 0.01 (objectness bias calibrated to ~1 %%, as a trained "
                                           "checkpoint)" % (n_candidates, plan.A)) if workload == "stream" else None,
                        "launches_per_step": launches,
-                       "host_issue_ms_per_step": round(host_issue_ms, 3),
+                       "host_issue_ms_per_step": None if host_issue_ms is None else round(host_issue_ms, 3),
                        "host_loop_ms_per_step": round(host_ms, 3),
                        "host_note": "host_issue = one step issued into empty queues (median of 5); host_loop = per step inside the "
                                     "timed loop, which includes blocking on full hardware queues while the GPU is the bottleneck"},
-            "roofline": roofline, "cpu_baseline": cpu, "parity": parity_record(args, workload, B), "extras": extras, "comm": comm,
+            "roofline": roofline, "cpu_baseline": cpu, "parity": parity_record(args, workload, B) if args.full else None, "extras": extras,
+            "comm": comm, "full": bool(args.full),
         }
         print(json.dumps(line))
     if dist is not None:

@@ -39,6 +39,8 @@ from .ops import View, EPI_LINEAR, CONV_DGRAD
 # Round 5: ON for the 16-bit modes together with 4 statistic replicas (l step 20.46-20.50 vs 20.64-20.67 ms, profiles/r05 stage l:
 # the replicas every workgroup of the apply pass re-reads shrink 8x, and -216 launches on the forward chains); the run-to-run
 # reproducibility that argued for 32 replicas is the exact mode's business now (one replica row per workgroup, bit-equal steps).
+# Round 7: the per-workgroup rows are the default in every dtype (EXACT_STATS below), and the fused launch cannot fold them, so it
+# runs only with STREAMYOLO_EXACT_STATS=0 (l step, 8 pairs, bf16, same box: 22.35-22.53 ms deterministic vs 19.39-19.44 ms).
 # "auto" (default): 16-bit compute dtypes only; "1" / "0": everywhere / nowhere (A/B timing).
 _FUSED_FINALIZE = __import__("os").environ.get("STREAMYOLO_FUSED_FINALIZE", "auto")
 # Round 5: the BatchNorm-backward REDUCE of a Bottleneck's 1x1 layer can ride in the epilogue of the 3x3 layer's data gradient (the
@@ -49,8 +51,9 @@ _FUSED_FINALIZE = __import__("os").environ.get("STREAMYOLO_FUSED_FINALIZE", "aut
 # kernels overlap: data gradients +0.6 ms, the l step 20.78-20.82 vs 20.68-20.75 ms (profiles/r05 stage m).  "1": on (A/B timing).
 BNR_FUSION = __import__("os").environ.get("STREAMYOLO_BNR_FUSION", "0") != "0"
 BNR_TILES = (98, 100, 101, 109, 104, 107, 117, 118)     # data-gradient tiles whose staged epilogue carries it (csrc/conv_igemm.hip)
-# exact (fp32) mode: one statistics replica row per workgroup -> run-to-run bit-equal steps (TrainPlan.__init__); "0" = the
-# replica counts of the speed modes (A/B switch)
+# one statistics replica row per workgroup -> run-to-run bit-equal steps in every compute dtype (TrainPlan.__init__; until round 7
+# the fp32 mode only: the 16-bit modes' shared replicas made the loss dict and SimOTA's decisions differ between identical steps);
+# "0" = the shared replica counts of the 16-bit speed modes (A/B switch)
 EXACT_STATS = __import__("os").environ.get("STREAMYOLO_EXACT_STATS", "1") != "0"
 # The workgroup cap of the BatchNorm-backward APPLY pass AS SCHEDULED in the step: the library's own default (1024) is that kernel's
 # optimum from round 2; beside round 5's frame chains and weight-gradient streams fewer, fatter workgroups leave the MFMA kernels
@@ -411,12 +414,12 @@ class TrainPlan:
         convs = [op for op in self.ops if op.kind == "conv"]
         tot_c = sum(op.y.C for op in convs)
         # Replicas of the statistics arrays, per conv.  Speed modes: STAT_COPIES / BWD_COPIES everywhere (fp32 atomics of many
-        # workgroups per replica: the sums depend on their arrival order in the last bits).  EXACT mode (fp32 compute, round 5):
+        # workgroups per replica: the sums depend on their arrival order in the last bits).  EXACT mode (the default in every dtype):
         # every workgroup gets a replica row of its own — one `0 + x` atomic per row and channel — and the finalize / fold
         # launches add the rows in index order, so two identical steps are bit-equal and SimOTA's discrete decisions
         # (tal_head.py:679-712) no longer flip between runs.  Rows: forward = pixel tiles of a frame's launch (<= N * H *
         # ceil(W / 32), whatever tile the tuner picks); backward reduce = its workgroup cap (SY_BN_REDUCE_BLOCKS, 768).
-        self.exact_stats = EXACT_STATS and self.dtype == ops.DT_F32
+        self.exact_stats = EXACT_STATS
         self.stat_copies = self.STAT_COPIES if self.STAT_COPIES > 0 else (32 if self.dtype == ops.DT_F32 else 4)
         # (never with the exact mode's one-row-per-workgroup statistics: sy_bn_finalize_apply does not fold the thousands of rows —
         #  only sy_bn_finalize's fold_rows_kernel does, and the running-statistics launch reads the folded rows — ADVICE r05)

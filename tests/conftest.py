@@ -10,6 +10,25 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run by the driver through gpurun)")
+    # the suite tunes shapes the committed tuner cache (streamyolo_amd/lib/tune_cache.json) does not hold: it starts from a
+    # copy of that file, so a test run leaves the tracked file as it was
+    if not os.environ.get("STREAMYOLO_TUNE_CACHE"):
+        import shutil
+        import tempfile
+        config._tune_dir = tempfile.mkdtemp(prefix="sy_tune_")
+        copy = os.path.join(config._tune_dir, "tune_cache.json")
+        src = os.path.join(ROOT, "streamyolo_amd", "lib", "tune_cache.json")
+        if os.path.exists(src):
+            shutil.copyfile(src, copy)
+        os.environ["STREAMYOLO_TUNE_CACHE"] = copy
+
+
+def pytest_unconfigure(config):
+    d = getattr(config, "_tune_dir", None)
+    if d:
+        import shutil
+        shutil.rmtree(d, ignore_errors=True)
+        os.environ.pop("STREAMYOLO_TUNE_CACHE", None)
 
 
 def pytest_collection_modifyitems(config, items):

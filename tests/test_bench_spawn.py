@@ -88,3 +88,32 @@ def test_bench_never_prints_a_one_gpu_line_for_gpus_n(emu_built):
                        env=_env(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_line_and_dump_outputs_repeat(emu_built, tmp_path):
+    """A plain 1-GPU line carries the headline only (no roofline / host issue / parity / CPU baseline / extras), and
+    --dump-outputs writes the last timed step's losses, gradient sample and running statistics as float32 / float64 .npy files
+    within 64 MB; two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + ARGS + ["--dump-outputs", str(d)],
+                           env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=400)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _json_line(r.stdout)
+        assert line["steps"] == 1 and line["ms_per_step"] > 0 and line["full"] is False
+        assert all(line[key] is None for key in ("roofline", "cpu_baseline", "parity", "extras"))
+        assert line["config"]["host_issue_ms_per_step"] is None
+        files = sorted(os.listdir(d))
+        assert files == sorted(["bn_running_stats.npy", "cls_loss.npy", "conf_loss.npy", "grad_sample.npy", "grad_sample_index.npy",
+                                "iou_loss.npy", "l1_loss.npy", "num_fg.npy", "total_loss.npy"])
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["grad_sample"].size == arrays["grad_sample_index"].size > 0 and np.abs(arrays["grad_sample"]).max() > 0
+        assert np.isfinite(arrays["total_loss"]).all() and arrays["total_loss"][0] > 0
+        dumps.append(arrays)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

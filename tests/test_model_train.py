@@ -655,6 +655,19 @@ def test_exact_mode_steps_are_bit_equal(name, B, H, W):
     owns a replica row (TrainPlan.exact_stats) and the loss partials are added in index order (tal_finish_kernel), so nothing
     depends on the arrival order of atomics.  The reference's step is deterministic for a given input (tal_head.py:679-712
     is a pure function of the predictions); until round 5 one SimOTA decision flipped in ~2 of 5 identical runs here."""
+    _identical_steps_are_bit_equal(name, B, H, W, "fp32")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_16bit_steps_are_bit_equal(dtype):
+    """The same in the 16-bit modes (the dtype bench.py times): their statistics take one replica row per workgroup as well
+    (TrainPlan.exact_stats), so the 16-bit MFMA tiles, the split-K weight gradients and the loss kernel leave no order-dependent
+    sum behind either."""
+    _identical_steps_are_bit_equal("l", 2, 288, 480, dtype)
+
+
+def _identical_steps_are_bit_equal(name, B, H, W, dtype):
     from streamyolo_amd import _lib
     _lib.use_library(_lib.DEFAULT_PATH)
     dev = torch.device("cuda:0")
@@ -663,7 +676,7 @@ def test_exact_mode_steps_are_bit_equal(name, B, H, W):
     x = synth_frames(B, H, W, seed=2).to(dev)
     lab, sup = synth_labels(B, H, W, cfg.num_classes, num_gt=12, seed=3)
     lab, sup = lab.to(dev), sup.to(dev)
-    model = sy.build_model(name).to(dev).train().set_compute_dtype("fp32")
+    model = sy.build_model(name).to(dev).train().set_compute_dtype(dtype)
     model.head.use_l1 = True
     runs = []
     for _ in range(4):                                       # run 0 tunes, run 1 records the tape, runs 2-3 replay it

@@ -9,7 +9,7 @@
 #   tests[:K_EXPR[:ARGS]]        pytest tests -m gpu -q [-k "K_EXPR" with + for spaces] [args] -> pytest_gpu.log, parity_table.json
 #   tenv:K=V,K=V:K_EXPR          the same subset under environment switches                 -> pytest_gpu_env.log
 #   smoke                        __graft_entry__.smoke()                                -> smoke.log
-#   bench:NAME[:ARGS]            python bench.py ARGS                                   -> bench_NAME.json
+#   bench:NAME[:ARGS]            python bench.py --full ARGS                            -> bench_NAME.json
 #   benv:NAME:K=V,K=V[:ARGS]     same with environment variables (A/B switches)         -> bench_NAME.json
 #   prof[:ARGS]                  rocprofv3 --kernel-trace --stats of bench.py (train l, 5 steps) -> kernel_stats.csv, rocprof_last_step.txt
 #   traffic[:WORKLOAD[:MODEL]]   PMC HBM-traffic passes (tools/pmc_traffic.py)          -> traffic_WORKLOAD_MODEL.{json,txt}
@@ -38,9 +38,9 @@ for task in "$@"; do
         tenv)  (env ${a//,/ } timeout 900 python -m pytest tests -m gpu -q -k "${b//+/ }" 2>&1 | grep -vE "$noise") > $O/pytest_gpu_env.log 2>&1
                grep -E "passed|failed|error" $O/pytest_gpu_env.log | tail -3 ;;
         smoke) (timeout 600 python __graft_entry__.py smoke 2>&1 | grep -vE "$noise" | tail -2) > $O/smoke.log 2>&1; cat $O/smoke.log ;;
-        bench) (timeout 900 python bench.py ${b//,/ } 2>$O/bench_$a.err | tail -1) > $O/bench_$a.json
+        bench) (timeout 900 python bench.py --full ${b//,/ } 2>$O/bench_$a.err | tail -1) > $O/bench_$a.json
                python tools/bench_line.py $O/bench_$a.json ;;
-        benv)  (env ${b//,/ } timeout 900 python bench.py ${c//,/ } 2>$O/bench_$a.err | tail -1) > $O/bench_$a.json
+        benv)  (env ${b//,/ } timeout 900 python bench.py --full ${c//,/ } 2>$O/bench_$a.err | tail -1) > $O/bench_$a.json
                python tools/bench_line.py $O/bench_$a.json ;;
         prof)  rm -rf /tmp/prof_$STAGE
                (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$STAGE -- python $OLDPWD/bench.py --workload train --model l --steps 5 --warmup 4 --no-cpu-baseline --extras 0 ${a//,/ } 2>&1 | tail -1) > $O/rocprof_bench_line.json 2>&1
