@@ -238,6 +238,36 @@ typedef struct sy_optim_entry {
 SY_API int sy_sgd_ema_step(const sy_optim_entry* entries, int n_entries, int total_chunks, float lr, float momentum,
                            float grad_scale, float ema_decay, int first_step, void* stream);
 
+/* ---- dynamic loss scaling without a host read -----------------------------------------------------------------
+ * Replaces `self.scaler.scale(loss).backward(); self.scaler.step(self.optimizer); self.scaler.update()` of the reference's
+ * --fp16 trainer (exps/train_utils/double_trainer.py:113-119) on the fused path: torch.amp.GradScaler's rule, with its state in
+ * DEVICE memory.  Every entry point below takes a device POINTER to the state and reads it inside the kernel: a launch tape
+ * stores argument values, so a scale passed by value would be frozen at recording time; a pointer is read anew at every replay.
+ * One iteration:  sy_tal_loss_scaled (gradients = scale x true gradients)  ->  backward pass  ->  [all-reduce]  ->
+ * sy_grad_nonfinite  ->  sy_sgd_ema_step_scaled  ->  sy_loss_scale_update.  Added to ABI 7 (nothing existing changed). */
+typedef struct sy_scaler_state {
+    float scale;                /* the loss scale S the next sy_tal_loss_scaled multiplies d_raw by                      */
+    float inv_scale;            /* (float)(1.0 / (double)S), as GradScaler.unscale_ computes it; kept by sy_loss_scale_update */
+    int32_t growth_tracker;     /* consecutive taken steps since the last change of S (GradScaler._growth_tracker)       */
+    int32_t found_inf;          /* set to 1 by sy_grad_nonfinite, read by sy_sgd_ema_step_scaled, cleared by the update  */
+    int32_t steps_taken;        /* iterations whose parameter update was applied                                         */
+    int32_t steps_skipped;      /* iterations skipped because a gradient was inf / nan                                   */
+    int32_t reserved[2];
+} sy_scaler_state;
+/* found_inf = 1 if any gradient element of the table (entries with g != NULL; same table and chunk0 prefix as
+ * sy_sgd_ema_step) is +-inf or nan; denormals and FLT_MAX are finite.  One read of the gradients, nothing else written. */
+SY_API int sy_grad_nonfinite(const sy_optim_entry* entries, int n_entries, int total_chunks, void* scaler_state, void* stream);
+/* sy_sgd_ema_step with grad_scale = extra_scale * state->inv_scale (extra_scale: 1/world_size when the caller has not divided
+ * yet) and the parameter / momentum half applied only when state->found_inf == 0; the EMA half runs either way, on the
+ * (possibly unchanged) parameter — the reference calls ema_model.update after a skipped scaler.step too.  There is no first_step
+ * flag (the host cannot know whether step 0 was skipped): momentum buffers must start ZEROED, 0*momentum + d == d. */
+SY_API int sy_sgd_ema_step_scaled(const sy_optim_entry* entries, int n_entries, int total_chunks, float lr, float momentum,
+                                  float extra_scale, float ema_decay, const void* scaler_state, void* stream);
+/* GradScaler.update(): found_inf ? (S *= backoff, tracker = 0, ++steps_skipped)
+ *                                : (++steps_taken; ++tracker == growth_interval ? (S *= growth if that is finite, tracker = 0) : -);
+ * then found_inf = 0 and inv_scale recomputed.  One single-thread launch. */
+SY_API int sy_loss_scale_update(void* scaler_state, float growth_factor, float backoff_factor, int growth_interval, void* stream);
+
 /* Per-step weight staging: the nn.Parameters stay OIHW fp32 (the optimizer's master copy,
  * exps/train_utils/double_trainer.py:114-119); ONE launch re-derives, for every convolution of the step, the
  * layouts the MFMA kernels read.  Entry: a source block w[co_n][ci_n][taps] fp32 written as rows r0..r0+co_n of
@@ -340,6 +370,15 @@ SY_API int sy_tal_loss(const float* raw, int B, int A, int num_classes, const fl
                        const int32_t* level_w, const float* level_stride, int nlevels, float gamma,
                        float ignore_thr, float ignore_value, int use_l1, float* d_raw, float* losses,
                        int32_t* fg_mask, void* workspace, void* d_pad, int pad_dtype, void* stream);
+/* The same launches with the loss scale folded in (GradScaler.scale(loss).backward(), double_trainer.py:113-114): every element
+ * of d_raw and d_pad is multiplied by scaler_state->scale (device sy_scaler_state; in fp32, before d_pad's conversion) where it
+ * is written; losses[0..7] stay the TRUE loss.  scaler_state == NULL: sy_tal_loss, bit for bit. */
+SY_API int sy_tal_loss_scaled(const float* raw, int B, int A, int num_classes, const float* labels,
+                              const float* support, int max_labels, const int32_t* level_h,
+                              const int32_t* level_w, const float* level_stride, int nlevels, float gamma,
+                              float ignore_thr, float ignore_value, int use_l1, float* d_raw, float* losses,
+                              int32_t* fg_mask, void* workspace, void* d_pad, int pad_dtype, const void* scaler_state,
+                              void* stream);
 
 /* Assignment of the LAST sy_tal_loss call on `workspace` (same B, A, max_labels): matched_gt [B, A] int32 = index of the matched
  * ground truth of every anchor, -1 for background; matched_iou [B, A] fp32 = its IoU (either may be NULL).  The reference's

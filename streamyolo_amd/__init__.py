@@ -5,6 +5,7 @@ Public surface mirrors the reference's exps/model package:
 Every numeric result comes from hand-written HIP kernels (streamyolo_amd/csrc) behind a C ABI
 (include/streamyolo_hip.h); importing this package without the built library fails on first use.
 """
+from .amp import DeviceGradScaler
 from .model.darknet import CSPDarknet
 from .model.dfp_pafpn import DFPPAFPN
 from .model.pipe_head import PIPEHead
@@ -12,7 +13,7 @@ from .model.tal_head import TALHead
 from .model.yolox import YOLOX
 from .postprocess import postprocess
 
-__all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model"]
+__all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model", "DeviceGradScaler"]
 __version__ = "0.1.0"
 
 MODEL_ZOO = {

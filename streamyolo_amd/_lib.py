@@ -59,6 +59,12 @@ class PackEntry(C.Structure):
                 ("tile0", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ScalerState(C.Structure):
+    """sy_scaler_state (include/streamyolo_hip.h): 32 bytes of DEVICE memory."""
+    _fields_ = [("scale", C.c_float), ("inv_scale", C.c_float), ("growth_tracker", C.c_int32), ("found_inf", C.c_int32),
+                ("steps_taken", C.c_int32), ("steps_skipped", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class OptimEntry(C.Structure):
     """sy_optim_entry (include/streamyolo_hip.h)."""
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("buf", C.c_void_p), ("ema", C.c_void_p), ("n", C.c_int64),
@@ -103,6 +109,9 @@ SIGNATURES = {
     "sy_head_decode": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
     "sy_postprocess": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
     "sy_sgd_ema_step": (_I, [_P, _I, _I, _F, _F, _F, _F, _I, _P]),
+    "sy_grad_nonfinite": (_I, [_P, _I, _I, _P, _P]),
+    "sy_sgd_ema_step_scaled": (_I, [_P, _I, _I, _F, _F, _F, _F, _P, _P]),
+    "sy_loss_scale_update": (_I, [_P, _F, _F, _I, _P]),
     "sy_pack_weights": (_I, [_P, _I, _I, _P]),
     "sy_bn_running_update": (_I, [_P, _I, _I, _P]),
     "sy_bn_finalize": (_I, [_P, _P, _I, _I, _D, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I, _P]),
@@ -112,6 +121,7 @@ SIGNATURES = {
     "sy_bn_silu_bwd_apply": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _L, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sy_tal_loss_workspace_bytes": (_L, [_I, _I, _I]),
     "sy_tal_loss": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P, _I, _P]),
+    "sy_tal_loss_scaled": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _F, _F, _F, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
     "sy_tal_loss_assignment": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "sy_zero_rows": (_I, [_P, _L, _L, _L, _P]),
     "sy_bn_grid_caps": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -453,10 +453,12 @@ __global__ __launch_bounds__(256) void tal_grad_kernel(const float* raw, int B, 
                                                        int max_labels, TalGeom geom, float gamma, int use_l1,
                                                        const unsigned char* ws, TalLayout L,
                                                        float* d_raw, float* losses, int* fg_mask, void* d_pad, int pad_dtype,
-                                                       float* block_part) {
+                                                       float* block_part, const sy_scaler_state* scaler) {
     SY_TL_BEGIN(14);
     __shared__ float s_tot[8];
     __shared__ float s_acc[4][4];
+    // loss scale (sy_tal_loss_scaled): read from DEVICE memory at every launch — a taped replay sees the scale of this iteration
+    const float loss_scale = scaler != nullptr ? scaler->scale : 1.0f;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // batch totals of the per-image partial sums (every workgroup recomputes them: B is small)
     if (tid < 8) {
@@ -481,6 +483,7 @@ __global__ __launch_bounds__(256) void tal_grad_kernel(const float* raw, int B, 
         // d(total)/d(raw) of channel k: the fp32 row, and (optional) the same value in the MFMA operand layout of the backward pass's
         // first kernels, [reg 4 | obj | 0 0 0 | cls nc] x 16 in the compute dtype (the columns in between stay zero)
         auto put = [&](int k, float v) {
+            v = v * loss_scale;                                // x 1.0f is exact: the unscaled entry point keeps its bits
             d_row[k] = v;
             if (d_pad != nullptr) {
                 const long long o = i * 16 + (k < 5 ? k : 3 + k);
@@ -602,10 +605,11 @@ extern "C" int64_t sy_tal_loss_workspace_bytes(int B, int A, int max_gt) {
     return tal_layout(A, max_gt).image_bytes * (int64_t)B + kGradBlocksMax * 4 * (int64_t)sizeof(float);   // + tal_grad_kernel's partial rows
 }
 
-extern "C" int sy_tal_loss(const float* raw, int B, int A, int num_classes, const float* labels, const float* support,
+static int tal_loss_launch(const float* raw, int B, int A, int num_classes, const float* labels, const float* support,
                            int max_labels, const int32_t* level_h, const int32_t* level_w, const float* level_stride,
                            int nlevels, float gamma, float ignore_thr, float ignore_value, int use_l1, float* d_raw,
-                           float* losses, int32_t* fg_mask, void* workspace, void* d_pad, int pad_dtype, void* stream) {
+                           float* losses, int32_t* fg_mask, void* workspace, void* d_pad, int pad_dtype,
+                           const sy_scaler_state* scaler, void* stream) {
     if (raw == nullptr || labels == nullptr || support == nullptr || d_raw == nullptr || losses == nullptr ||
         workspace == nullptr || level_h == nullptr || level_w == nullptr || level_stride == nullptr)
         return SY_ERR_ARG;
@@ -635,9 +639,29 @@ extern "C" int sy_tal_loss(const float* raw, int B, int A, int num_classes, cons
     if (blocks > kGradBlocksMax) blocks = kGradBlocksMax;
     float* const block_part = reinterpret_cast<float*>((unsigned char*)workspace + L.image_bytes * (long long)B);
     SY_LAUNCH(tal_grad_kernel, dim3(blocks), dim3(256), 0, stream, raw, B, A, num_classes, labels, max_labels, g, gamma,
-              use_l1, (const unsigned char*)workspace, L, d_raw, losses, fg_mask, d_pad, pad_dtype, block_part);
+              use_l1, (const unsigned char*)workspace, L, d_raw, losses, fg_mask, d_pad, pad_dtype, block_part, scaler);
     SY_LAUNCH(tal_finish_kernel, dim3(1), dim3(256), 0, stream, (const float*)block_part, blocks, losses);
     return SY_LAUNCH_OK() == 0 ? SY_OK : SY_ERR_LAUNCH;
+}
+
+extern "C" int sy_tal_loss(const float* raw, int B, int A, int num_classes, const float* labels, const float* support,
+                           int max_labels, const int32_t* level_h, const int32_t* level_w, const float* level_stride,
+                           int nlevels, float gamma, float ignore_thr, float ignore_value, int use_l1, float* d_raw,
+                           float* losses, int32_t* fg_mask, void* workspace, void* d_pad, int pad_dtype, void* stream) {
+    return tal_loss_launch(raw, B, A, num_classes, labels, support, max_labels, level_h, level_w, level_stride, nlevels, gamma,
+                           ignore_thr, ignore_value, use_l1, d_raw, losses, fg_mask, workspace, d_pad, pad_dtype, nullptr, stream);
+}
+
+// The loss half of GradScaler.scale(loss).backward() (double_trainer.py:113-114): the same five launches, tal_grad_kernel
+// multiplying every gradient element by the device-resident scale where it writes it.
+extern "C" int sy_tal_loss_scaled(const float* raw, int B, int A, int num_classes, const float* labels, const float* support,
+                                  int max_labels, const int32_t* level_h, const int32_t* level_w, const float* level_stride,
+                                  int nlevels, float gamma, float ignore_thr, float ignore_value, int use_l1, float* d_raw,
+                                  float* losses, int32_t* fg_mask, void* workspace, void* d_pad, int pad_dtype,
+                                  const void* scaler_state, void* stream) {
+    return tal_loss_launch(raw, B, A, num_classes, labels, support, max_labels, level_h, level_w, level_stride, nlevels, gamma,
+                           ignore_thr, ignore_value, use_l1, d_raw, losses, fg_mask, workspace, d_pad, pad_dtype,
+                           (const sy_scaler_state*)scaler_state, stream);
 }
 // Read-out of the last sy_tal_loss call's assignment (tests / diagnostics): per anchor the matched ground-truth index (-1 =
 // background) and its IoU, as the reference's get_assignments returns them (tal_head.py:559-600: matched_gt_inds,

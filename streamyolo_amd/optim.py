@@ -83,15 +83,30 @@ class FusedSGDEMA:
     def _sig(self):
         return tuple((p.data_ptr(), None if p.grad is None else p.grad.data_ptr()) for p in self.params)
 
-    def step(self, lr, grad_scale=1.0):
+    def step(self, lr, grad_scale=1.0, scaler=None):
         """One iteration: SGD update of every parameter from its .grad, then the EMA update (decay from the update
-        counter, as ModelEMA.update).  `grad_scale` multiplies the gradients first (1/loss_scale, 1/world_size)."""
+        counter, as ModelEMA.update).  `grad_scale` multiplies the gradients first (1/loss_scale, 1/world_size).
+        scaler (amp.DeviceGradScaler; the gradients are `scale x` the true ones, TrainStep.step(..., scaler)): three launches on
+        this stream and no host read — look for inf / nan, the same update with the gradients divided by the scale and skipped
+        if one was found (the EMA still advances, as ema_model.update does after a skipped scaler.step), then GradScaler.update's
+        rule on the device state.  In data-parallel runs this comes after the gradient all-reduce: a sum carries any rank's
+        inf / nan to every rank, so all ranks take the same decision."""
         if self._sig() != self._table_sig:                       # a .grad or parameter moved: re-point the table
             self._sd_ptr = {v.data_ptr(): k for k, v in self.model.state_dict().items()}
             self._build(self._wd, self.model.state_dict())
         assert all(p.grad is not None for p in self.params), "FusedSGDEMA.step: a parameter has no gradient"
         self.updates += 1
         d = self.ema_base * (1.0 - math.exp(-self.updates / 2000.0)) if self.ema_keys else 0.0
+        if scaler is not None and scaler.enabled:
+            scaler.check_gradients(self.table, self.n, self.chunks)
+            # no first_step here (step 0 may be the skipped one): self.buf starts zeroed, 0 * momentum + d == d
+            ops.check(_lib.lib().sy_sgd_ema_step_scaled(self.table.data_ptr(), self.n, self.chunks, float(lr), float(self.momentum),
+                                                        float(grad_scale), float(d), scaler.state(self.device).data_ptr(),
+                                                        ops.stream_of(self.table)), "sy_sgd_ema_step_scaled")
+            scaler.update()
+            self.steps += 1
+            ops.bump_weights_epoch()
+            return
         ops.check(_lib.lib().sy_sgd_ema_step(self.table.data_ptr(), self.n, self.chunks, float(lr), float(self.momentum),
                                              float(grad_scale), float(d), 1 if self.steps == 0 else 0,
                                              ops.stream_of(self.table)), "sy_sgd_ema_step")

@@ -854,9 +854,10 @@ class TrainPlan:
                        y_ld=nch, y_bs=self.A * nch, cout=self.nc)
 
     # ------------------------------------------------------------------------------------------------
-    def loss(self, labels, support):
+    def loss(self, labels, support, scaler=None):
         """SimOTA + Trend-Aware loss and d(total)/d(raw) in two HIP kernels, no host sync (sy_tal_loss).
-        Returns (loss dict of 0-dim device tensors, d_raw [B, A, 5+nc])."""
+        Returns (loss dict of 0-dim device tensors, d_raw [B, A, 5+nc]).  scaler (amp.DeviceGradScaler): d_raw and its packed copy
+        are `scale x` the true gradient (sy_tal_loss_scaled reads the scale on the device), the loss dict is the true loss."""
         head = self.head
         if self.loss_ws is None or self.loss_ws.max_labels != labels.shape[1]:
             self.loss_ws = ops.TalLossWorkspace(self.B, self.A, 5 + self.nc, self.hw, head.strides, self.device,
@@ -867,7 +868,8 @@ class TrainPlan:
         pad = self.dpad if self.nc <= 8 else None
         self._zero_gradient_arenas()
         losses, d_raw, _ = ops.tal_loss(self.raw, labels, support, self.nc, head.gamma, head.ignore_thr,
-                                        head.ignore_value, head.use_l1, self.loss_ws, d_pad=pad)
+                                        head.ignore_value, head.use_l1, self.loss_ws, d_pad=pad,
+                                        scaler_state=None if scaler is None else scaler.state(self.device))
         self._packed_for = (d_raw, d_raw._version) if pad is not None else None     # identity AND content: an in-place scaling repacks
         out = {"total_loss": losses[0], "iou_loss": losses[1], "l1_loss": losses[2], "conf_loss": losses[3],
                "cls_loss": losses[4], "num_fg": losses[5]}
@@ -1501,6 +1503,7 @@ class TrainStep:
         # on ROCm 7 replaying this ~1500-node graph costs MORE host time than the launch tapes (measured)
         self.use_graph = (os.environ.get("STREAMYOLO_GRAPH", "0") != "0") if graph is None else bool(graph)
         self.graph = None
+        self.gscaler = None                         # device address of the scaler state the graph was captured with
         self.eager_steps = 0
         self.comm = None                            # stream the bucket all-reduces are issued from
         model.train()
@@ -1534,14 +1537,14 @@ class TrainStep:
                 p.grad = plan.gview[id(p)]
         return plan
 
-    def _eager(self, x, lab, sup):
+    def _eager(self, x, lab, sup, scaler=None):
         plan = self.plan
         plan.forward(x)
-        out, d_raw = plan.loss(lab, sup)
+        out, d_raw = plan.loss(lab, sup, scaler)
         plan.backward(d_raw)
         return out
 
-    def _capture(self, x, lab, sup):
+    def _capture(self, x, lab, sup, scaler=None):
         """Record the step into a hipGraph over static copies of the inputs.  The side-stream forks join back inside
         forward() / backward(), so the capture is one connected graph whose independent branches may run concurrently."""
         if isinstance(x, FramePairsU8):
@@ -1550,10 +1553,16 @@ class TrainStep:
         self.gx, self.glab, self.gsup = x.float().contiguous().clone(), lab.clone(), sup.clone()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self.gout = self._eager(self.gx, self.glab, self.gsup)
-        self.graph = g
+            self.gout = self._eager(self.gx, self.glab, self.gsup, scaler)
+        self.graph, self.gscaler = g, (None if scaler is None else scaler.state(self.plan.device).data_ptr())
 
-    def step(self, x, targets):
+    def step(self, x, targets, scaler=None):
+        """scaler (amp.DeviceGradScaler): the gradients left in the arena are `scale x` the true ones — the loss launch reads the
+        scale from the scaler's device state (no host read, no extra launch); FusedSGDEMA.step(lr, scaler=...) checks, unscales
+        and applies them.  The forward / backward tapes hold no scale-dependent launch and are shared with scaler=None steps; a
+        captured hipGraph contains the loss launch and is keyed by the scaler's state."""
+        if scaler is not None and not scaler.enabled:
+            scaler = None
         plan = self._ensure(x)
         self._last = (x, targets)
         lab, sup = split_targets(self.model, targets)
@@ -1562,8 +1571,9 @@ class TrainStep:
         graphable = self.use_graph and x.is_cuda and plan.run_table is not None and plan.tuned
         if self.graph is not None and not (plan.cache.valid() and plan.run_table.valid()):
             self.graph = None                                   # a parameter / buffer moved: the recording is stale
-        if graphable and self.eager_steps >= 2 and (self.graph is None or self.glab.shape != lab.shape):
-            self._capture(x, lab, sup)
+        gkey = None if scaler is None else scaler.state(plan.device).data_ptr()
+        if graphable and self.eager_steps >= 2 and (self.graph is None or self.glab.shape != lab.shape or self.gscaler != gkey):
+            self._capture(x, lab, sup, scaler)
         if graphable and self.graph is not None:
             self.gx.copy_(x)
             self.glab.copy_(lab)
@@ -1571,7 +1581,7 @@ class TrainStep:
             self.graph.replay()
             out = self.gout
         else:
-            out = self._eager(x, lab, sup)
+            out = self._eager(x, lab, sup, scaler)
             self.eager_steps += 1
         self.last_overlapped = len(self._reduced)               # buckets whose all-reduce started DURING backward
         if self.world > 1:
