@@ -402,6 +402,33 @@ SY_API int sy_zero_rows(void* ptr, int64_t rows, int64_t row_bytes, int64_t pitc
 SY_API int sy_view_copy(const void* in, int ldi, void* out, int ldo, int64_t pixels, int C, int dtype,
                  int accumulate, void* stream);
 
+/* ---- per-stream DFP state of a batched streaming tick (many cameras, one on_pipe plan) ------------------------------
+ * Stand in, per batch row, for the `buffer` hand-over of dfp_pafpn.py:211-228: a camera's previous pre-fusion PAN outputs
+ * live in slot s of a dense pool [n_slots][H][W][C] per level.  row_slot (int32 [B]) and row_first (uint8 [B]) are DEVICE
+ * tables read inside the kernels — a launch tape replays argument values, the tables' CONTENT is read anew at every replay
+ * (the mechanism of sy_scaler_state): row_slot[b] < 0 (or >= n_slots) = row b carries no frame this tick, row_first[b] != 0 =
+ * row b starts a sequence.  Views as in sy_conv2d: ld = pixel pitch, bs = batch stride, both in elements; every 16-byte piece
+ * must be aligned (pointers, C, ld and bs x element size multiples of 16), else SY_ERR_ARG.  Any dtype (pure data movement).
+ * Added to ABI 7 (nothing existing changed).
+ *
+ * sy_stream_state_gather, one level (dfp_pafpn.py:211-214 per row): sup[b] <- pool[row_slot[b]] when the row has a slot and
+ * does not start a sequence, else cur[b] (node 'star': the frame fuses with itself; inactive rows too, so that nothing
+ * uninitialised is read). */
+SY_API int sy_stream_state_gather(const void* cur, int ld_cur, int64_t cur_bs, const void* pool, int n_slots, void* sup,
+                                  int ld_sup, int64_t sup_bs, int B, int H, int W, int C, const int32_t* row_slot,
+                                  const uint8_t* row_first, int dtype, void* stream);
+/* sy_stream_state_scatter, all levels in one launch (dfp_pafpn.py:226-228, `buffer_` kept for the next frame, per row):
+ * pool_k[row_slot[b]] <- cur_k[b] for every level k of the table and every row with a slot; other rows write nothing.
+ * `levels` is HOST memory (n_levels <= 8), validated and copied into the launch.  A slot must not appear in two rows. */
+typedef struct sy_stream_level {
+    const void* cur;        /* this level's pre-fusion PAN output view [B, H, W, C]           */
+    void* pool;             /* dense [n_slots, H, W, C]                                       */
+    int64_t bs;             /* batch stride of `cur`, elements                                */
+    int32_t H, W, C, ld;    /* ld = pixel pitch of `cur`, elements                            */
+} sy_stream_level;
+SY_API int sy_stream_state_scatter(const sy_stream_level* levels, int n_levels, int n_slots, int B, const int32_t* row_slot,
+                                   int dtype, void* stream);
+
 /* backward of sy_resize_nearest (scatter-add into the source grid) */
 SY_API int sy_resize_nearest_bwd(const void* dout, int N, int Ho, int Wo, int C, int lddo, int64_t dobs,
                           void* din, int Hi, int Wi, int lddi, int64_t dibs, int accumulate,

@@ -71,6 +71,12 @@ class OptimEntry(C.Structure):
                 ("weight_decay", C.c_float), ("lr_mult", C.c_float), ("chunk0", C.c_int32), ("reserved", C.c_int32)]
 
 
+class StreamLevel(C.Structure):
+    """sy_stream_level (include/streamyolo_hip.h)."""
+    _fields_ = [("cur", C.c_void_p), ("pool", C.c_void_p), ("bs", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
+                ("C", C.c_int32), ("ld", C.c_int32)]
+
+
 def pack_table(rows):
     """ctypes array of PackEntry with the tile0 prefix filled in -> (array, total_tiles)."""
     t = 0
@@ -126,6 +132,8 @@ SIGNATURES = {
     "sy_zero_rows": (_I, [_P, _L, _L, _L, _P]),
     "sy_bn_grid_caps": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sy_view_copy": (_I, [_P, _I, _P, _I, _L, _I, _I, _I, _P]),
+    "sy_stream_state_gather": (_I, [_P, _I, _L, _P, _I, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "sy_stream_state_scatter": (_I, [_P, _I, _I, _I, _P, _I, _P]),
     "sy_splitk_epilogue": (_I, [_P, _I, _L, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "sy_rows_add_f32": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
     "sy_pred_grad_fold_workspace_floats": (_L, [_I]),

@@ -352,6 +352,7 @@ class InferencePlan:
         self.decode = decode
         self.cache = ParamCache(self.dtype, device)
         self._stream_tape, self._tape_param_list = None, None
+        self._slots_tape = None                      # run_stream_slots_taped's tape (per-stream state, batched tick)
         self._rec = None                             # open native tape (run_stream_taped)
         # split-K for the deep small-map 3x3 layers of the streaming step (36-72 workgroups at batch 1): opt-in, because the
         # fp32 summation order differs from the single-pass kernel (the facade's off_pipe == chained on_pipe bit-identity is
@@ -477,6 +478,7 @@ class InferencePlan:
         self._splitk_ws = torch.empty((3 if self._stream_order is not None else 1, max(need, 4 << 20)), dtype=torch.float32,
                                       device=self.device)
         self._stream_tape = None                                     # recorded pointers are stale
+        self._slots_tape = None
         return True
 
     # -- execution --------------------------------------------------------------------------------
@@ -683,6 +685,88 @@ class InferencePlan:
             prog[2].replay(ops.stream_of(self.out), self._chain_streams[0].cuda_stream, more=(self._chain_streams[1].cuda_stream,))
         return prog[3]
 
+    # ---- batched tick over per-stream state ------------------------------------------------------------------
+    def run_stream_slots(self, x, state):
+        """Streaming step of a batch whose rows belong to DIFFERENT cameras (`state`: StreamSlots).  Row b fuses with the PAN
+        outputs kept in pool slot state.row_slot[b], or with itself where state.row_first[b] is set (node 'star',
+        dfp_pafpn.py:211-214, per row) or the row carries no frame (slot < 0); afterwards the rows with a slot keep their
+        current PAN outputs there (:226).  Which row is which is DATA the two kernels read on the device: the launch list is
+        the same for every tick, first frames included, so a recorded tape serves them all."""
+        assert not self.pair and state.B == self.B and state.dtype == self.dtype
+        if isinstance(x, FramePairsU8):
+            x.pack_focus(self.f0)
+        else:
+            ops.focus_pack(x.float().contiguous(), 0, self.f0)
+        n_fuse = 6
+        fuse = self.ops[self.n_backbone_ops - n_fuse:self.n_backbone_ops]
+        level_of = {id(op): k for k, op in enumerate(fuse[0::2])}     # a level's gather goes in front of its two fusion convs
+
+        def gather(k):
+            ops.stream_state_gather(self.cur_pans[k], state.pools[k], self.sup_in[k], state.row_slot, state.row_first)
+        self._in_stream = True
+        try:
+            if self._rec is not None and self._stream_order is not None:
+                chain = 0
+                for e in self._stream_order:
+                    if e[0] == "dep":
+                        self._mark("dep", (e[1], e[2]))
+                        continue
+                    if e[2] != chain:
+                        chain = e[2]
+                        self._mark("cur", chain)
+                    if id(e[1]) in level_of and e[3] is None:
+                        gather(level_of[id(e[1])])
+                    self._run_op(e[1], e[3])
+                self._mark("cur", 0)
+                if not self.decode:
+                    ops.head_decode(self.out, boxes=False, obj_sigmoid=True)
+                out = self.out
+            else:
+                for op in self.ops[:self.n_backbone_ops - n_fuse]:
+                    self._run_op(op)
+                for op in fuse:
+                    if id(op) in level_of:
+                        gather(level_of[id(op)])
+                    self._run_op(op)
+                out = self.run_head()
+        finally:
+            self._in_stream = False
+        # behind the join of the chains: the gathers of the side chains read the pools this launch rewrites
+        ops.stream_state_scatter(self.cur_pans, state.pools, state.row_slot)
+        return out
+
+    def run_stream_slots_taped(self, x, state, post=None):
+        """run_stream_slots(x, state) [+ post(out)] from a launch tape, as run_stream_taped: recorded by the first call over a
+        given input buffer, state and `post`, replayed by ONE C call afterwards — whatever the tables hold.  Weights are
+        taken as frozen (streaming inference)."""
+        assert not self.pair and self.decode
+        if not (isinstance(x, FramePairsU8) or (x.dtype == torch.float32 and x.is_contiguous())):
+            raise ValueError("run_stream_slots_taped needs a FramePairsU8 or a contiguous fp32 frame (no conversion kernels on the tape)")
+        sig = self._tape_signature(x, False)
+        prog = self._slots_tape
+        from . import _lib
+        if prog is None or prog[0] != sig or prog[1] is not post or prog[4] is not state:
+            self._ensure_tuned()
+            tape = _lib.NativeTape()
+            self._ws_grew = False
+            with tape:
+                self._rec = tape
+                try:
+                    out = self.run_stream_slots(x, state)
+                    res = post(out) if post is not None else out
+                finally:
+                    self._rec = None
+            self._slots_tape = None if self._ws_grew else (sig, post, tape, res, state)
+            ops.save_tuned()
+            return res
+        if self._stream_order is None or not self.out.is_cuda:
+            prog[2].replay(ops.stream_of(self.out), None)
+        else:
+            if self._chain_streams is None:
+                self._chain_streams = [torch.cuda.Stream(self.device), torch.cuda.Stream(self.device)]
+            prog[2].replay(ops.stream_of(self.out), self._chain_streams[0].cuda_stream, more=(self._chain_streams[1].cuda_stream,))
+        return prog[3]
+
     def export_buffer(self):
         """The current frame's PRE-fusion PAN outputs as NCHW-shaped (channels-last memory) tensors:
         what the reference returns as `buffer_` (dfp_pafpn.py:226) and takes back next frame."""
@@ -733,6 +817,53 @@ class InferencePlan:
         for kind, a, b in evs:
             totals[kind] = totals.get(kind, 0.0) + a.elapsed_time(b)
         return {k: v / iters for k, v in totals.items()}
+
+
+class StreamSlots:
+    """Per-stream DFP state of a batched on_pipe plan (InferencePlan.run_stream_slots): one pool [S, H_k, W_k, C_k] per PAN level
+    in the plan's compute dtype — slot s = one camera's pre-fusion PAN outputs of its previous frame — and the tick's two
+    device tables, row_slot int32 [B] (pool slot of batch row b, -1 = the row carries no frame) and row_first uint8 [B] (the
+    row starts a sequence).  The tables are two windows of ONE device buffer with pinned host mirrors of the same layout:
+    upload() is a single non-blocking copy."""
+
+    def __init__(self, plan, n_slots):
+        assert not plan.pair and plan.cur_pans is not None and n_slots >= 1
+        self.B, self.S, self.dtype, self.device = plan.B, int(n_slots), plan.dtype, plan.device
+        B = self.B
+        self.pools = [torch.zeros((self.S, p.H, p.W, p.C), dtype=p.buf.dtype, device=plan.device) for p in plan.cur_pans]
+        self.tables = torch.zeros(8 * B, dtype=torch.uint8, device=plan.device)
+        self.row_slot = self.tables[:4 * B].view(torch.int32)
+        self.row_first = self.tables[4 * B:5 * B]
+        # a ring of host mirrors: an upload still in flight keeps reading its mirror while the next tick's rows are written
+        self._ring = [torch.zeros(8 * B, dtype=torch.uint8) for _ in range(4 if self.tables.is_cuda else 1)]
+        if self.tables.is_cuda:
+            self._ring = [h.pin_memory() for h in self._ring]
+        self._done = [None] * len(self._ring)
+        self._at = 0
+        self.set_rows((), ())
+
+    def set_rows(self, slots, firsts):
+        """Rows 0..n-1 of the next tick (host side only): their pool slots and first flags; rows n..B-1 inactive."""
+        n, B = len(slots), self.B
+        assert n <= B and len(firsts) == n and all(0 <= s < self.S for s in slots) and len(set(slots)) == n
+        self._at = (self._at + 1) % len(self._ring)
+        if self._done[self._at] is not None:
+            self._done[self._at].synchronize()                       # (only when the device is a whole ring of ticks behind)
+        host = self._ring[self._at]
+        host_slot, host_first = host[:4 * B].view(torch.int32), host[4 * B:5 * B]
+        host_slot.fill_(-1)
+        host_first.zero_()
+        for b, (s, f) in enumerate(zip(slots, firsts)):
+            host_slot[b] = int(s)
+            host_first[b] = 1 if f else 0
+
+    def upload(self):
+        """The rows of the last set_rows -> the device tables: ONE non-blocking copy on the current stream."""
+        self.tables.copy_(self._ring[self._at], non_blocking=True)
+        if self.tables.is_cuda:
+            ev = self._done[self._at] or torch.cuda.Event()
+            ev.record()
+            self._done[self._at] = ev
 
 
 def _nhwc_of(t, like):

@@ -285,6 +285,42 @@ def view_copy(src, dst, accumulate=False):
                                   1 if accumulate else 0, stream_of(src.buf)), "sy_view_copy")
 
 
+def _stream_tables(row_slot, row_first, B, device):
+    assert row_slot.dtype == torch.int32 and row_slot.is_contiguous() and row_slot.numel() >= B and row_slot.device == device
+    if row_first is not None:
+        assert row_first.dtype == torch.uint8 and row_first.is_contiguous() and row_first.numel() >= B and row_first.device == device
+
+
+def stream_state_gather(cur, pool, sup, row_slot, row_first):
+    """One PAN level of a batched streaming tick: sup[b] <- pool[row_slot[b]] for rows that continue a sequence, cur[b] for rows
+    that start one (row_first[b] != 0) or carry no frame (row_slot[b] < 0).  cur / sup: Views [B, H, W, C]; pool: dense tensor
+    [S, H, W, C] in their dtype; row_slot int32 [B], row_first uint8 [B]: device tensors, read by the kernel at run time."""
+    assert (cur.N, cur.H, cur.W, cur.C) == (sup.N, sup.H, sup.W, sup.C) and cur.dtype == sup.dtype
+    assert pool.dim() == 4 and tuple(pool.shape[1:]) == (cur.H, cur.W, cur.C) and pool.is_contiguous() and pool.dtype == cur.buf.dtype
+    _stream_tables(row_slot, row_first, cur.N, pool.device)
+    check(_lib.lib().sy_stream_state_gather(cur.ptr(), cur.ld, cur.bs, pool.data_ptr(), pool.shape[0], sup.ptr(), sup.ld, sup.bs,
+                                            cur.N, cur.H, cur.W, cur.C, row_slot.data_ptr(), row_first.data_ptr(), cur.dtype,
+                                            stream_of(pool)), "sy_stream_state_gather")
+
+
+def stream_state_scatter(curs, pools, row_slot):
+    """Every PAN level in one launch: pools[k][row_slot[b]] <- curs[k][b] for the rows with a slot (row_slot[b] >= 0); the other
+    rows write nothing.  curs: Views [B, H_k, W_k, C_k]; pools: dense tensors [S, H_k, W_k, C_k]; one dtype, one S."""
+    assert len(curs) == len(pools) and 1 <= len(curs) <= 8
+    B, S, dt = curs[0].N, pools[0].shape[0], curs[0].dtype
+    rows = []
+    for c, p in zip(curs, pools):
+        assert c.N == B and c.dtype == dt and p.dim() == 4 and tuple(p.shape) == (S, c.H, c.W, c.C) and p.is_contiguous()
+        assert p.dtype == c.buf.dtype
+        e = _lib.StreamLevel()
+        e.cur, e.pool, e.bs, e.H, e.W, e.C, e.ld = c.ptr(), p.data_ptr(), c.bs, c.H, c.W, c.C, c.ld
+        rows.append(e)
+    _stream_tables(row_slot, None, B, pools[0].device)
+    arr = (_lib.StreamLevel * len(rows))(*rows)
+    check(_lib.lib().sy_stream_state_scatter(arr, len(rows), S, B, row_slot.data_ptr(), dt, stream_of(pools[0])),
+          "sy_stream_state_scatter")
+
+
 def rows_add_f32(dst, src, rows, cols, ldd, lds, zero_src=False):
     """dst[r][:cols] += src[r][:cols] (fp32, row pitches ldd / lds in elements); zero_src: clear the source behind the read."""
     assert dst.dtype == torch.float32 and src.dtype == torch.float32

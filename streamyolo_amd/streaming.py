@@ -3,6 +3,7 @@
 Mirrors, name for name where the reference has a name:
   inference()                 sAP/streamyolo/streamyolo_det.py:62-83     decoded output -> (boxes / in_scale, scores, labels, None)
   StreamingDetector           streamyolo_det.py:96-124, :176-181         model.half() on_pipe loop state (buffer), warm-up, one frame
+  MultiStreamDetector         the same loop state for MANY cameras       one batched on_pipe plan, per-stream buffers in device pools
   run_sequence()              streamyolo_det.py:138-199                  the real-time scheduling loop of one sequence
   runtime_summary()           streamyolo_det.py:201-229 + sAP/util print_stats   timing statistics
   pair_with_ground_truth()    sAP/streamyolo/streaming_eval.py:74-139    time-based prediction / ground-truth pairing -> COCO dicts
@@ -18,6 +19,7 @@ import time
 import numpy as np
 import torch
 
+from . import ops
 from .data import FramePairsU8
 from .postprocess import postprocess_device
 
@@ -103,6 +105,151 @@ class StreamingDetector:
             # steady state: the ~140 launches of the frame (pack, network, decode, NMS) replayed from a launch tape
             det, _, cnt = self.plan.run_stream_taped(self._in, post=self._post, check_params=False)
             return _parse(det, cnt, self.in_scale)
+
+
+class MultiStreamDetector:
+    """StreamingDetector for many cameras at once: ONE on_pipe plan of `batch` rows serves whichever of up to `max_streams`
+    open streams have a frame ready.  Every stream keeps its own `buffer` (streamyolo_det.py:150, :180: reset at its sequence
+    start, carried from its previous frame) as a slot of per-level device pools; a tick names, per batch row, the slot it
+    belongs to and whether its sequence starts here, in two small device tables the state kernels read
+    (sy_stream_state_gather / _scatter).  Cameras need not tick in lockstep: a stream that has no frame in a tick is simply
+    not in it, and its state stays as it is.  First frames are data, not control flow: after warm_up() every tick is one
+    replay of the same launch tape.
+
+        det = MultiStreamDetector(model, (1200, 1920), max_streams=16, batch=8); det.warm_up()
+        a, b = det.open(), det.open()
+        (boxes_a, scores_a, labels_a, _), (boxes_b, scores_b, labels_b, _) = det([frame_a, frame_b], [a, b])
+
+    All streams share one frame size.  Which frames go into a tick is the caller's scheduling policy."""
+
+    def __init__(self, model, frame_hw, max_streams=16, batch=8, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65,
+                 dtype="fp16", device="cuda"):
+        if int(batch) < 1 or int(max_streams) < 1:
+            raise ValueError("MultiStreamDetector: batch and max_streams must be positive")
+        self.model = model.to(device).eval().set_compute_dtype(dtype)
+        self.device = torch.device(device)
+        self.in_scale, self.batch, self.max_streams = in_scale, int(batch), int(max_streams)
+        self.frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
+        self.canvas = (int(self.frame_hw[0] * in_scale), int(self.frame_hw[1] * in_scale))      # streamyolo_det.py:177
+        if self.canvas[0] % 2 or self.canvas[1] % 2:
+            raise ValueError("MultiStreamDetector: in_scale %r gives an odd %dx%d network input (the Focus stem needs even sizes)"
+                             % (in_scale, self.canvas[0], self.canvas[1]))
+        if self.canvas == self.frame_hw:
+            self.decimate = 1
+        elif (2 * self.canvas[0], 2 * self.canvas[1]) == self.frame_hw:
+            self.decimate = 2
+        else:
+            self.decimate = -1
+        self.num_classes, self.conf_thre, self.nms_thresh = num_classes, conf_thre, nms_thresh
+        # detector-owned staging: row b of a tick's frames (rows without a frame keep stale pixels; their outputs are ignored)
+        self._stage = torch.zeros((self.batch,) + self.frame_hw + (3,), dtype=torch.uint8, device=self.device)
+        self._in = FramePairsU8(self._stage, None, self.canvas, self.decimate)
+        split_k = str(dtype) not in ("fp32", "torch.float32") and os.environ.get("STREAMYOLO_STREAM_SPLITK", "1") != "0"
+        self.plan = model._plans.inference(model.backbone, model.head, "on_pipe", self._in, owner=model, split_k=split_k)
+        from .engine import StreamSlots
+        self.state = StreamSlots(self.plan, self.max_streams)
+        self._ws = ops.PostprocessWorkspace(self.batch, self.plan.A, self.device)          # its own: results live until the next tick
+        self._post = lambda out: ops.postprocess(out, num_classes, conf_thre, nms_thresh, self._ws)   # one object: part of the tape key
+        self._slot_of = {}                                       # open stream id -> pool slot
+        self._first = {}                                         # open stream id -> its next frame starts a sequence
+        self._free = list(range(self.max_streams))
+        self._next_id = 0                                        # ids are never reused: a closed id stays invalid
+
+    # ---- stream bookkeeping (host side only) --------------------------------------------------------------------
+    def open(self):
+        """A new stream: its id.  Its first frame fuses with itself (`buffer = None`, streamyolo_det.py:150)."""
+        if not self._free:
+            raise RuntimeError("MultiStreamDetector: all %d streams are open" % self.max_streams)
+        sid = self._next_id
+        self._next_id += 1
+        self._slot_of[sid] = self._free.pop(0)
+        self._first[sid] = True
+        return sid
+
+    def _known(self, sid):
+        if sid not in self._slot_of:
+            raise ValueError("MultiStreamDetector: stream id %r is not open" % (sid,))
+
+    def reset(self, sid):
+        """A new sequence starts on stream `sid`: its next frame fuses with itself."""
+        self._known(sid)
+        self._first[sid] = True
+
+    def close(self, sid):
+        """Stream `sid` ends: its slot is free for the next open()."""
+        self._known(sid)
+        self._free.append(self._slot_of.pop(sid))
+        self._free.sort()
+        del self._first[sid]
+
+    def warm_up(self, n=10):
+        """streamyolo_det.py:113-120 on a dummy batch (no row carries a frame: no stream's state is written); builds, tunes and
+        records the plan.  Afterwards every open stream starts a new sequence."""
+        self._stage.fill_(1)
+        self.state.set_rows((), ())
+        self.state.upload()
+        with torch.no_grad():
+            for _ in range(max(int(n), 2)):                      # (a tuning + recording tick, then at least one replay)
+                self.plan.run_stream_slots_taped(self._in, self.state, post=self._post)
+        torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
+        for sid in self._first:
+            self._first[sid] = True
+
+    # ---- ticks -----------------------------------------------------------------------------------------------
+    def _check(self, frames, sids):
+        """Everything that can be wrong with a call, found BEFORE anything is written."""
+        if len(frames) != len(sids):
+            raise ValueError("MultiStreamDetector: %d frames for %d stream ids" % (len(frames), len(sids)))
+        fs = []
+        for f in frames:
+            f = torch.as_tensor(f)
+            if f.dtype != torch.uint8 or tuple(f.shape) != self.frame_hw + (3,):
+                raise ValueError("MultiStreamDetector: frames must be uint8 [%d, %d, 3], got %s %s"
+                                 % (self.frame_hw + (f.dtype, tuple(f.shape))))
+            fs.append(f)
+        for t0 in range(0, len(sids), self.batch):
+            tick = list(sids[t0:t0 + self.batch])
+            for sid in tick:
+                self._known(sid)
+            if len(set(tick)) != len(tick):
+                raise ValueError("MultiStreamDetector: a stream id appears twice in one tick: %r" % (tick,))
+        return fs
+
+    def _tick(self, frames, sids):
+        n = len(sids)
+        for b, f in enumerate(frames):
+            self._stage[b].copy_(f, non_blocking=True)
+        self.state.set_rows([self._slot_of[s] for s in sids], [self._first[s] for s in sids])
+        self.state.upload()
+        for s in sids:
+            self._first[s] = False
+        with torch.no_grad():
+            det, _, cnt = self.plan.run_stream_slots_taped(self._in, self.state, post=self._post)
+        return det, cnt, n
+
+    def detect_device(self, frames, sids):
+        """One tick (len(frames) <= batch) without any host read: (det [batch, A, 7], cnt [batch], rows) — rows 0..rows-1 of
+        the device tensors belong to `sids` in order (kept detections det[b, :cnt[b]]: x1, y1, x2, y2 on the network input,
+        obj, class_conf, class), the other rows are meaningless.  The tensors are detector-owned and overwritten by the next
+        tick.  Frames are copied into the staging tensor, the tables go up in one non-blocking copy from pinned memory."""
+        if len(sids) > self.batch:
+            raise ValueError("MultiStreamDetector: %d frames in one tick of batch %d" % (len(sids), self.batch))
+        return self._tick(self._check(frames, sids), list(sids))
+
+    def __call__(self, frames, sids):
+        """n camera frames (uint8 [H, W, 3] arrays or tensors) and the ids of their streams -> n (bboxes, scores, labels, None)
+        host tuples in the order given, each what StreamingDetector returns for that frame.  n > batch: consecutive ticks.
+        Every tick ends with the device synchronised by the copy of its counts and kept rows."""
+        fs, sids = self._check(frames, sids), list(sids)
+        res = []
+        for t0 in range(0, len(sids), self.batch):
+            det, cnt, n = self._tick(fs[t0:t0 + self.batch], sids[t0:t0 + self.batch])
+            counts = cnt[:n].cpu().numpy()
+            rows = det[:n, :max(int(counts.max()), 1)].cpu().numpy()
+            for b in range(n):
+                d = rows[b, :int(counts[b])]
+                res.append((d[:, :4] / self.in_scale, d[:, 4] * d[:, 5], d[:, 6].astype(np.int32), None))
+        return res
 
 
 def run_sequence(frames, detect, fps=30.0, det_stride=1, dynamic_schedule=False, clock=time.perf_counter, reset=None):

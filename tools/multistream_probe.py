@@ -1,0 +1,145 @@
+#!/usr/bin/env python
+"""Batched streaming ticks of MultiStreamDetector against the same number of single-camera frames.
+
+StreamYOLO-l, fp16, 1200x1920 uint8 camera frames already on the device (the pattern of `bench.py --workload stream
+--u8-input 1`: 2x decimation + Focus packing, network, decode, NMS with a realistic candidate count; no host read inside the
+timed region).  Reports ms per tick and frames/s for batch in {1, 2, 4, 8, 16} with every row active, for n in {1, 4, 8} active
+rows at batch 8, and — the yardstick — for StreamingDetector's taped frame issued n times back to back.  Warm-up ticks (they
+build, tune and record the plans), then `--ticks` timed ticks between two events, `--rounds` times alternating with the
+yardstick; the best round counts.  Prints one JSON line (and writes it to --out).
+
+    python tools/multistream_probe.py --out profiles/r08/multistream_probe.json
+    python tools/multistream_probe.py --trace 8      # only warm up batch 8 and run 20 ticks (for rocprofv3 --kernel-trace --stats)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="l")
+    ap.add_argument("--dtype", default="fp16")
+    ap.add_argument("--height", type=int, default=1200)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--batches", default="1,2,4,8,16")
+    ap.add_argument("--active", default="1,4,8", help="active rows measured at batch 8")
+    ap.add_argument("--ticks", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--trace", type=int, default=0, help="batch: warm up, run 20 ticks of that batch and exit (profiler runs)")
+    ap.add_argument("--baseline-only", type=int, default=0, help="1: only the single-camera yardstick (also runs on older trees)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+    import streamyolo_amd as sy
+    from oracle import streamyolo_oracle as O
+    from streamyolo_amd import _lib
+    from streamyolo_amd.streaming import StreamingDetector
+    from streamyolo_amd.utils.synth import synth_state_dict, synth_frames
+    _lib.use_library(_lib.DEFAULT_PATH)
+    dev = torch.device("cuda:0")
+    hw = (args.height, args.width)
+    cfg = O.OracleConfig.named(args.model)
+    model = sy.build_model(args.model)
+    model.load_state_dict(synth_state_dict(O.param_shapes(cfg), seed=0), strict=True)
+    batches = [int(b) for b in args.batches.split(",") if b]
+    nmax = max(batches + [8])
+    # distinct pictures per row, every pixel repeated 2x2 so that the decimation returns the synthetic frame
+    x = synth_frames(nmax, hw[0] // 2, hw[1] // 2, seed=2)[:, 0:3]
+    raw = x.round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1)
+    raw = raw.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2).contiguous().to(dev)
+    frames = [raw[i] for i in range(nmax)]
+
+    single = StreamingDetector(model, hw, dtype=args.dtype, device=dev)
+    # a trained StreamYOLO passes ~1 % of its anchors through conf 0.01, random weights all of them: shift the objectness biases
+    # by one constant found by bisection on the first frame's own scores (bench.py --candidates realistic)
+    with torch.no_grad():
+        single._slot[0].copy_(frames[0])
+        dec = single.plan.run_stream(single._in, first=True).clone()
+        obj, cls = dec[0, :, 4].double().clamp(1e-12, 1 - 1e-12), dec[0, :, 5:].double().max(dim=1).values
+        logit = torch.log(obj / (1 - obj))
+        lo, hi = -40.0, 0.0
+        for _ in range(40):
+            mid = 0.5 * (lo + hi)
+            frac = float(((torch.sigmoid(logit + mid) * cls) >= 0.01).double().mean())
+            lo, hi = (mid, hi) if frac < 0.01 else (lo, mid)
+        for conv in model.head.obj_preds:
+            conv.bias.add_(0.5 * (lo + hi))
+    single.warm_up(args.warmup)
+
+    def single_tick(n):
+        with torch.no_grad():
+            for i in range(n):
+                single._slot[0].copy_(frames[i], non_blocking=True)
+                single.plan.run_stream_taped(single._in, post=single._post, check_params=False)
+
+    def timed(fn, ticks):
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        a.record()
+        for _ in range(ticks):
+            fn()
+        host = (time.perf_counter() - t0) * 1e3 / ticks
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / ticks, host
+
+    res = {"tool": "multistream_probe", "model": args.model, "dtype": args.dtype, "frame": list(hw), "ticks": args.ticks,
+           "warmup": args.warmup, "rounds": args.rounds, "kernel_source_key": _lib.kernel_source_key(),
+           "device": torch.cuda.get_device_name(0), "rows": []}
+
+    def emit():
+        line = json.dumps(res)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)) or ".", exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return line
+
+    if args.baseline_only:
+        single_tick(1)
+        for n in sorted(set(batches + [int(v) for v in args.active.split(",") if v])):
+            ms = min(timed(lambda: single_tick(n), args.ticks)[0] for _ in range(args.rounds))
+            res["rows"].append({"batch": 1, "active": n, "single_ms_per_tick": ms, "single_frames_per_s": 1e3 * n / ms})
+        print(emit())
+        return
+
+    from streamyolo_amd.streaming import MultiStreamDetector
+    single_tick(1)                                               # (steady state: the tape is recorded)
+    for B in ([args.trace] if args.trace else batches):
+        det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+        det.warm_up(args.warmup)
+        sids = [det.open() for _ in range(B)]
+        det.detect_device(frames[:B], sids)                      # first rows done: steady state
+        for n in ([B] if (B != 8 or args.trace) else sorted(set([int(v) for v in args.active.split(",") if v] + [B]))):
+            def multi_tick():
+                det.detect_device(frames[:n], sids[:n])
+            if args.trace:
+                timed(multi_tick, 20)
+                print(json.dumps({"traced_batch": B, "ticks": 20}))
+                return
+            multi_tick()
+            best_m, best_s, host_m = float("inf"), float("inf"), float("inf")
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                m, h = timed(multi_tick, args.ticks)
+                s, _ = timed(lambda: single_tick(n), args.ticks)
+                best_m, best_s, host_m = min(best_m, m), min(best_s, s), min(host_m, h)
+            res["rows"].append({"batch": B, "active": n, "ms_per_tick": best_m, "frames_per_s": 1e3 * n / best_m,
+                                "host_ms_per_tick": host_m, "single_ms_per_tick": best_s,
+                                "single_frames_per_s": 1e3 * n / best_s, "tick_over_n_single_frames": best_m / best_s})
+            emit()
+        del det                                                  # (its plan and pools go back to the allocator)
+    print(emit())
+
+
+if __name__ == "__main__":
+    main()
