@@ -72,6 +72,14 @@ def _schedule_bn_caps():
     return ops.bn_grid_caps(bwd_apply=BN_BAPPLY_BLOCKS_SCHEDULED)["bwd_reduce"]
 
 
+def exact_stat_rows(N, H, W):
+    """Statistics replica rows per segment that give EVERY workgroup of a forward convolution over an [N, H, W] output a row of its
+    own, whatever tile the tuner picks: no kernel cuts the pixels finer than one image row x 32 columns (the window kernels tile
+    TH >= 1 rows x 32 pixels of one image, the implicit-GEMM / 1x1 kernels >= 64 consecutive pixels).  tests/test_bn_statistics_exact.py
+    holds every forward tile code to it."""
+    return N * H * ((W + 31) // 32)
+
+
 # Measured and REMOVED in round 4 (profiles/r04/README.md): BatchNorm finalisation by the producing convolution's last workgroup
 # (every statistics launch got 8-13 us slower — each workgroup waits for its own atomics and a ticket round trip — the l step
 # 22.6-23.9 vs 22.3-23.0 ms at 2 ... 32 replicas) and BatchNorm backward as one resident launch whose workgroups wait for each
@@ -429,7 +437,7 @@ class TrainPlan:
         def copies_of(op):
             if not self.exact_stats:
                 return self.stat_copies, self.BWD_COPIES
-            return max(self.stat_copies, op.y.N * op.y.H * ((op.y.W + 31) // 32)), max(self.BWD_COPIES, reduce_cap)
+            return max(self.stat_copies, exact_stat_rows(op.y.N, op.y.H, op.y.W)), max(self.BWD_COPIES, reduce_cap)
         for op in convs:
             op.stat_copies, op.bwd_copies = copies_of(op)
         self.stat_arena = torch.zeros(2 * sum(op.stat_copies * op.y.C for op in convs), dtype=torch.float32, device=device)  # [sum | sumsq] x copies
