@@ -179,6 +179,24 @@ SY_API int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, int 
                              int row_stride, int decimate, const uint8_t* mirror, int H, int W, int Ho, int Wo,
                              int layout, void* out_cur, void* out_sup, int dtype, void* stream);
 
+/* The same pipeline with one frame source PER BATCH ROW, read on the device: cameras of different resolutions in one batch
+ * (MultiStreamDetector's mixed mode).  rows: B descriptors in DEVICE memory; row b of out_cur is bit for bit what
+ * sy_frames_u8_pack writes for that frame alone (same Hs, Ws, decimate, mirror, H, W, Ho, Wo, layout, dtype; sup = NULL).
+ * ONE launch whose grid depends on (B, Ho, Wo, layout) only, so a recorded launch serves any table contents.  A row with
+ * cur == NULL or Hs == 0 has no frame: the plain 114 canvas, nothing is read.  The host cannot see the table: the caller
+ * validates it (every frame addressable for Hs rows of row_stride >= 3 Ws bytes; decimate as above); a descriptor that
+ * sy_frames_u8_pack would refuse is written as a row without a frame, never read through.
+ * layout SY_FRAMES_NCHW: out_cur = fp32 [B, 3, Ho, Wo] (dtype = SY_DT_F32); SY_FRAMES_FOCUS: [B, Ho/2, Wo/2, 16] of `dtype`. */
+typedef struct sy_frame_src {      /* 32 bytes */
+    const uint8_t* cur;            /* [Hs, Ws, 3] BGR; NULL or Hs == 0: the row has no frame */
+    int32_t Hs, Ws, row_stride;    /* row_stride in bytes */
+    int32_t decimate;              /* 1 | 2 | 0 | -1, exactly as sy_frames_u8_pack */
+    int32_t mirror;                /* != 0: image[:, ::-1] */
+    int32_t reserved;
+} sy_frame_src;
+SY_API int sy_frames_u8_pack_rows(const sy_frame_src* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,
+                                  int dtype, void* stream);
+
 /* Exp.preprocess's multi-scale resize on the reference's own tensor: fp32 NCHW [N, C, H, W] -> [N, C, Ho, Wo],
  * torch bilinear, align_corners=False (cfgs/l_s50_onex_dfp_tal_filp.py:161-172).  C = 3 or 6. */
 SY_API int sy_resize_bilinear_nchw(const float* in, int N, int C, int H, int W, float* out, int Ho, int Wo, void* stream);

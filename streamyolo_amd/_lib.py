@@ -71,6 +71,12 @@ class OptimEntry(C.Structure):
                 ("weight_decay", C.c_float), ("lr_mult", C.c_float), ("chunk0", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FrameSrc(C.Structure):
+    """sy_frame_src (include/streamyolo_hip.h): 32 bytes of DEVICE memory per batch row."""
+    _fields_ = [("cur", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("row_stride", C.c_int32),
+                ("decimate", C.c_int32), ("mirror", C.c_int32), ("reserved", C.c_int32)]
+
+
 class StreamLevel(C.Structure):
     """sy_stream_level (include/streamyolo_hip.h)."""
     _fields_ = [("cur", C.c_void_p), ("pool", C.c_void_p), ("bs", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
@@ -106,6 +112,7 @@ SIGNATURES = {
     "sy_conv2d_wgrad": (_I, [C.POINTER(WgradDesc), _P]),
     "sy_focus_pack": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sy_frames_u8_pack": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "sy_frames_u8_pack_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sy_resize_bilinear_nchw": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "sy_resize_nearest": (_I, [_P, _I, _I, _I, _I, _I, _L, _P, _I, _I, _I, _L, _I, _P]),
     "sy_resize_nearest_bwd": (_I, [_P, _I, _I, _I, _I, _I, _L, _P, _I, _I, _I, _L, _I, _I, _P]),

@@ -26,53 +26,117 @@
 
 namespace {
 
-struct FrameSrc {               // uint8 HWC frames of one batch: current and (optional) support
-    const unsigned char* img[2];
-    long long image_stride;     // bytes between images
+// One frame after the load-time resize: what the per-pixel sampling needs besides the pixels.  Resolved from the camera size, the
+// decimate mode and the canvas by frame_geom() — on the host for sy_frames_u8_pack (one geometry per batch), on the device for
+// sy_frames_u8_pack_rows (one per batch row, from its descriptor): the same function, the same double arithmetic.
+struct FrameGeom {
     int row_stride;             // bytes between rows
     int hs, ws;                 // size AFTER the load-time resize (decimation or general ratio)
     int dec;                    // 1 or 2; 0 = general-ratio fixed-point bilinear from a src_h x src_w frame
     int src_h, src_w;
     double scale_y, scale_x;    // dec == 0: source / destination size ratios (OpenCV: 1. / ((double)dst / src))
-    const unsigned char* mirror;    // [B] flags or nullptr
-    // OpenCV's INTER_LINEAR tap set of one destination coordinate (resize.cpp, 8-bit fixed-point path)
-    struct Tap { int s0, s1; int a0, a1; };
-    // HORIZ: OpenCV zeroes the fraction at the left / right border (xofs / alpha tables); the vertical pass keeps the fraction
-    // and only clamps the two row indices (srows[k] = clip(sy + k)) — both taps then read the same row with b0 + b1 = 2048
-    template <bool HORIZ> static __device__ __forceinline__ Tap tap(int d, double scale, int ssize) {
-        float f = (float)(((double)d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= (float)s;
-        if (HORIZ) {
-            if (s < 0) { f = 0.0f; s = 0; }
-            if (s >= ssize - 1) { f = 0.0f; s = ssize - 1; }
+};
+
+// decimate (1 | 2 | 0 | -1, range and evenness already checked) of an Hs x Ws frame on an H x W canvas -> hs, ws, dec, scales
+__host__ __device__ inline int frame_geom(int Hs, int Ws, int decimate, int H, int W, FrameGeom& g) {
+    int hs, ws;
+    g.src_h = Hs; g.src_w = Ws; g.scale_y = 1.0; g.scale_x = 1.0;
+    if (decimate == 0 || decimate == -1) {
+        if (decimate == 0) {
+            // preproc: r = min(H / h, W / w); resized to (int(w * r), int(h * r)) — the same double arithmetic as the Python code
+            const double r = ((double)H / Hs < (double)W / Ws) ? (double)H / Hs : (double)W / Ws;
+            hs = (int)(Hs * r); ws = (int)(Ws * r);
+        } else {
+            // streaming: cv2.resize(img, (w_img, h_img)) with the canvas = (int(h * in_scale), int(w * in_scale)) — each axis
+            // stretched on its own, no letterbox (sAP/streamyolo/streamyolo_det.py:176-178)
+            hs = H; ws = W;
+            decimate = 0;
         }
-        Tap t;
-        t.s0 = s < 0 ? 0 : (s > ssize - 1 ? ssize - 1 : s);
-        t.s1 = s + 1 < 0 ? 0 : (s + 1 > ssize - 1 ? ssize - 1 : s + 1);
-        t.a0 = (int)rintf((1.0f - f) * 2048.0f);            // saturate_cast<short>(float) = cvRound (round half to even)
-        t.a1 = (int)rintf(f * 2048.0f);
-        return t;
+        if (hs < 1 || ws < 1 || hs > H || ws > W) return SY_ERR_UNSUPPORTED;
+        g.scale_y = 1.0 / ((double)hs / Hs); g.scale_x = 1.0 / ((double)ws / Ws);
+        if (hs == Hs && ws == Ws) decimate = 1;                          // r == 1: cv::resize copies
+        else if (2 * hs == Hs && 2 * ws == Ws) decimate = 2;             // both factors exactly 2: OpenCV's INTER_AREA fast path
+    } else {
+        hs = Hs / decimate; ws = Ws / decimate;
+        // preproc's ratio r = min(H / h, W / w) must be exactly 1 after the decimation (see the header)
+        if (hs > H || ws > W || (hs != H && ws != W)) return SY_ERR_UNSUPPORTED;
     }
+    g.hs = hs; g.ws = ws; g.dec = decimate;
+    return SY_OK;
+}
+
+// OpenCV's INTER_LINEAR tap set of one destination coordinate (resize.cpp, 8-bit fixed-point path)
+struct Tap { int s0, s1; int a0, a1; };
+// HORIZ: OpenCV zeroes the fraction at the left / right border (xofs / alpha tables); the vertical pass keeps the fraction
+// and only clamps the two row indices (srows[k] = clip(sy + k)) — both taps then read the same row with b0 + b1 = 2048
+template <bool HORIZ> __device__ __forceinline__ Tap frame_tap(int d, double scale, int ssize) {
+    float f = (float)(((double)d + 0.5) * scale - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (HORIZ) {
+        if (s < 0) { f = 0.0f; s = 0; }
+        if (s >= ssize - 1) { f = 0.0f; s = ssize - 1; }
+    }
+    Tap t;
+    t.s0 = s < 0 ? 0 : (s > ssize - 1 ? ssize - 1 : s);
+    t.s1 = s + 1 < 0 ? 0 : (s + 1 > ssize - 1 ? ssize - 1 : s + 1);
+    t.a0 = (int)rintf((1.0f - f) * 2048.0f);            // saturate_cast<short>(float) = cvRound (round half to even)
+    t.a1 = (int)rintf(f * 2048.0f);
+    return t;
+}
+
+// value of channel c at (y, x) of the letterboxed canvas of the frame at p — the per-pixel arithmetic of BOTH pack kernels.
+// Reads stay inside src_h x src_w: dec 1 / 2 address rows < dec * hs <= src_h and bytes < dec * ws * 3 <= row_stride, the
+// bilinear taps are clamped to [0, src - 1].
+__device__ __forceinline__ float frame_at(const unsigned char* p, const FrameGeom& g, bool mirror, int c, int y, int x) {
+    if (y >= g.hs || x >= g.ws) return 114.0f;
+    if (mirror) x = g.ws - 1 - x;
+    if (g.dec == 1) return (float)p[(long long)y * g.row_stride + x * 3 + c];
+    if (g.dec == 0) {
+        const Tap ty = frame_tap<false>(y, g.scale_y, g.src_h), tx = frame_tap<true>(x, g.scale_x, g.src_w);
+        const unsigned char* r0 = p + (long long)ty.s0 * g.row_stride + c;
+        const unsigned char* r1 = p + (long long)ty.s1 * g.row_stride + c;
+        const int S0 = (int)r0[tx.s0 * 3] * tx.a0 + (int)r0[tx.s1 * 3] * tx.a1;      // horizontal pass, scaled by 2^11
+        const int S1 = (int)r1[tx.s0 * 3] * tx.a0 + (int)r1[tx.s1 * 3] * tx.a1;
+        const int v = (((ty.a0 * (S0 >> 4)) >> 16) + ((ty.a1 * (S1 >> 4)) >> 16) + 2) >> 2;
+        return (float)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    }
+    const unsigned char* r0 = p + (long long)(2 * y) * g.row_stride + (2 * x) * 3 + c;
+    const unsigned char* r1 = r0 + g.row_stride;
+    return (float)(((int)r0[0] + (int)r0[3] + (int)r1[0] + (int)r1[3] + 2) >> 2);
+}
+
+struct FrameSrc {               // uint8 HWC frames of one batch, one geometry: current and (optional) support
+    const unsigned char* img[2];
+    long long image_stride;     // bytes between images
+    FrameGeom g;
+    const unsigned char* mirror;    // [B] flags or nullptr
     // value of channel c at (y, x) of the letterboxed H x W canvas of image n, frame f
     __device__ __forceinline__ float at(int n, int f, int c, int y, int x) const {
-        if (y >= hs || x >= ws) return 114.0f;
-        if (mirror != nullptr && mirror[n]) x = ws - 1 - x;
-        const unsigned char* p = img[f] + n * image_stride;
-        if (dec == 1) return (float)p[(long long)y * row_stride + x * 3 + c];
-        if (dec == 0) {
-            const Tap ty = tap<false>(y, scale_y, src_h), tx = tap<true>(x, scale_x, src_w);
-            const unsigned char* r0 = p + (long long)ty.s0 * row_stride + c;
-            const unsigned char* r1 = p + (long long)ty.s1 * row_stride + c;
-            const int S0 = (int)r0[tx.s0 * 3] * tx.a0 + (int)r0[tx.s1 * 3] * tx.a1;      // horizontal pass, scaled by 2^11
-            const int S1 = (int)r1[tx.s0 * 3] * tx.a0 + (int)r1[tx.s1 * 3] * tx.a1;
-            const int v = (((ty.a0 * (S0 >> 4)) >> 16) + ((ty.a1 * (S1 >> 4)) >> 16) + 2) >> 2;
-            return (float)(v < 0 ? 0 : (v > 255 ? 255 : v));
-        }
-        const unsigned char* r0 = p + (long long)(2 * y) * row_stride + (2 * x) * 3 + c;
-        const unsigned char* r1 = r0 + row_stride;
-        return (float)(((int)r0[0] + (int)r0[3] + (int)r1[0] + (int)r1[3] + 2) >> 2);
+        if (y >= g.hs || x >= g.ws) return 114.0f;
+        return frame_at(img[f] + n * image_stride, g, mirror != nullptr && mirror[n], c, y, x);
     }
+};
+
+// One batch row of sy_frames_u8_pack_rows: its descriptor, resolved.  A row without a frame — or with a descriptor no frame can
+// have (the host cannot see the table: the caller validates it) — has hs = ws = 0: the plain 114 canvas, nothing is read.
+struct RowSrc {
+    const unsigned char* p;
+    FrameGeom g;
+    bool mirror;
+    __device__ __forceinline__ RowSrc(const sy_frame_src* rows, int b, int H, int W) {
+        const sy_frame_src d = rows[b];                         // one 32-byte load per workgroup (b = blockIdx.y: uniform)
+        p = nullptr; mirror = false;
+        g.row_stride = 0; g.hs = 0; g.ws = 0; g.dec = 1; g.src_h = 0; g.src_w = 0; g.scale_y = 1.0; g.scale_x = 1.0;
+        if (d.cur == nullptr || d.Hs <= 0 || d.Ws <= 0 || d.decimate < -1 || d.decimate > 2) return;
+        if ((d.decimate == 2 && ((d.Hs & 1) || (d.Ws & 1))) || (long long)d.row_stride < (long long)d.Ws * 3) return;
+        FrameGeom r;
+        if (frame_geom(d.Hs, d.Ws, d.decimate, H, W, r) != SY_OK) return;
+        r.row_stride = d.row_stride;
+        r.dec = sy_uniform(r.dec);                              // the sampling branches on it: scalar, the whole workgroup one way
+        g = r; p = d.cur; mirror = d.mirror != 0;
+    }
+    __device__ __forceinline__ float at(int, int, int c, int y, int x) const { return frame_at(p, g, mirror, c, y, x); }
 };
 
 struct PlaneSrc {               // fp32 NCHW tensor (Exp.preprocess's input)
@@ -124,11 +188,32 @@ __global__ __launch_bounds__(kBlock) void frames_to_nchw_kernel(S src, int B, in
     }
 }
 
+// one Focus-packed output pixel (h2, w2) of image n, frame f -> 16 elements at dst
+template <typename T, typename S>
+__device__ __forceinline__ void focus_pixel(const S& src, int n, int f, int h2, int w2, bool resize, float sy, float sx, int H, int W,
+                                            typename T::elem* dst_elems) {
+    typedef typename T::elem elem;
+    elem o[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int y = 2 * h2 + (q & 1), x = 2 * w2 + (q >> 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[q * 3 + c] = T::from_f32(sample(src, n, f, c, y, x, resize, sy, sx, H, W));
+    }
+#pragma unroll
+    for (int c = 12; c < 16; ++c) o[c] = T::from_f32(0.0f);
+    uint4* dst = reinterpret_cast<uint4*>(dst_elems);
+    constexpr int NV = (int)(16 * sizeof(elem) / 16);
+    uint4 v[NV];
+    __builtin_memcpy(v, o, sizeof(o));
+#pragma unroll
+    for (int k = 0; k < NV; ++k) dst[k] = v[k];
+}
+
 // -> Focus-packed NHWC16 [B, Ho/2, Wo/2, 16] per frame (12 real channels, q*3 + c with q = TL, BL, TR, BR; 4 zero)
 template <typename T, typename S>
 __global__ __launch_bounds__(kBlock) void frames_to_focus_kernel(S src, int B, int F, int H, int W, int Ho, int Wo,
                                                                  typename T::elem* out0, typename T::elem* out1) {
-    typedef typename T::elem elem;
     const bool resize = Ho != H || Wo != W;
     const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
     const int H2 = Ho >> 1, W2 = Wo >> 1;
@@ -139,22 +224,44 @@ __global__ __launch_bounds__(kBlock) void frames_to_focus_kernel(S src, int B, i
         const int w2 = (int)(r % W2);
         const int h2 = (int)((r / W2) % H2);
         const int n = (int)(r / ((long long)W2 * H2));
-        elem o[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int y = 2 * h2 + (q & 1), x = 2 * w2 + (q >> 1);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[q * 3 + c] = T::from_f32(sample(src, n, f, c, y, x, resize, sy, sx, H, W));
-        }
-#pragma unroll
-        for (int c = 12; c < 16; ++c) o[c] = T::from_f32(0.0f);
-        uint4* dst = reinterpret_cast<uint4*>((f == 0 ? out0 : out1) + r * 16);
-        constexpr int NV = (int)(16 * sizeof(elem) / 16);
-        uint4 v[NV];
-        __builtin_memcpy(v, o, sizeof(o));
-#pragma unroll
-        for (int k = 0; k < NV; ++k) dst[k] = v[k];
+        focus_pixel<T>(src, n, f, h2, w2, resize, sy, sx, H, W, (f == 0 ? out0 : out1) + r * 16);
     }
+}
+
+// ---- per-row sources (sy_frames_u8_pack_rows): blockIdx.y = the batch row, its workgroups stride over that row's outputs.
+// The grid depends on (B, Ho, Wo, layout) only: a recorded launch serves any table contents.
+__global__ __launch_bounds__(kBlock) void rows_to_nchw_kernel(const sy_frame_src* rows, int H, int W, int Ho, int Wo, float* out) {
+    const int n = blockIdx.y;
+    const RowSrc src(rows, n, H, W);
+    const bool resize = Ho != H || Wo != W;
+    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
+    const int per_row = 3 * Ho * Wo;
+    float* o = out + (long long)n * per_row;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < per_row; i += gridDim.x * kBlock) {
+        const int x = i % Wo, y = (i / Wo) % Ho, c = i / (Wo * Ho);
+        o[i] = sample(src, n, 0, c, y, x, resize, sy, sx, H, W);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void rows_to_focus_kernel(const sy_frame_src* rows, int H, int W, int Ho, int Wo,
+                                                               typename T::elem* out) {
+    const int n = blockIdx.y;
+    const RowSrc src(rows, n, H, W);
+    const bool resize = Ho != H || Wo != W;
+    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
+    const int H2 = Ho >> 1, W2 = Wo >> 1;
+    const int per_row = H2 * W2;
+    typename T::elem* o = out + (long long)n * per_row * 16;
+    for (int r = blockIdx.x * kBlock + threadIdx.x; r < per_row; r += gridDim.x * kBlock)
+        focus_pixel<T>(src, n, 0, r / W2, r % W2, resize, sy, sx, H, W, o + (long long)r * 16);
+}
+
+// workgroups per batch row: enough for the row's outputs, the whole grid capped like grid_for's
+inline dim3 rows_grid(long long per_row, int B) {
+    long long gx = (per_row + kBlock - 1) / kBlock, cap = (256 * 8 + B - 1) / B;
+    if (gx > cap) gx = cap;
+    return dim3((unsigned)(gx < 1 ? 1 : gx), (unsigned)B);
 }
 
 }  // namespace
@@ -167,32 +274,12 @@ extern "C" int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, 
     if (decimate < -1 || decimate > 2) return SY_ERR_UNSUPPORTED;
     if (decimate == 2 && ((Hs & 1) || (Ws & 1))) return SY_ERR_UNSUPPORTED;
     if (row_stride < Ws * 3 || image_stride < (int64_t)row_stride * Hs) return SY_ERR_ARG;
-    int hs, ws;
     FrameSrc src;
-    src.src_h = Hs; src.src_w = Ws; src.scale_y = 1.0; src.scale_x = 1.0;
-    if (decimate == 0 || decimate == -1) {
-        if (decimate == 0) {
-            // preproc: r = min(H / h, W / w); resized to (int(w * r), int(h * r)) — the same double arithmetic as the Python code
-            const double r = ((double)H / Hs < (double)W / Ws) ? (double)H / Hs : (double)W / Ws;
-            hs = (int)(Hs * r); ws = (int)(Ws * r);
-        } else {
-            // streaming: cv2.resize(img, (w_img, h_img)) with the canvas = (int(h * in_scale), int(w * in_scale)) — each axis
-            // stretched on its own, no letterbox (sAP/streamyolo/streamyolo_det.py:176-178)
-            hs = H; ws = W;
-            decimate = 0;
-        }
-        if (hs < 1 || ws < 1 || hs > H || ws > W) return SY_ERR_UNSUPPORTED;
-        src.scale_y = 1.0 / ((double)hs / Hs); src.scale_x = 1.0 / ((double)ws / Ws);
-        if (hs == Hs && ws == Ws) decimate = 1;                          // r == 1: cv::resize copies
-        else if (2 * hs == Hs && 2 * ws == Ws) decimate = 2;             // both factors exactly 2: OpenCV's INTER_AREA fast path
-    } else {
-        hs = Hs / decimate; ws = Ws / decimate;
-        // preproc's ratio r = min(H / h, W / w) must be exactly 1 after the decimation (see the header)
-        if (hs > H || ws > W || (hs != H && ws != W)) return SY_ERR_UNSUPPORTED;
-    }
+    const int rc = frame_geom(Hs, Ws, decimate, H, W, src.g);
+    if (rc != SY_OK) return rc;
     const int F = sup != nullptr ? 2 : 1;
-    src.img[0] = cur; src.img[1] = sup; src.image_stride = image_stride; src.row_stride = row_stride;
-    src.hs = hs; src.ws = ws; src.dec = decimate; src.mirror = mirror;
+    src.img[0] = cur; src.img[1] = sup; src.image_stride = image_stride; src.g.row_stride = row_stride;
+    src.mirror = mirror;
     if (layout == SY_FRAMES_NCHW) {
         const long long work = (long long)B * F * 3 * Ho * Wo;
         SY_LAUNCH((frames_to_nchw_kernel<FrameSrc>), dim3(grid_for(work)), dim3(kBlock), 0, stream, src, B, F, H, W, Ho, Wo,
@@ -204,6 +291,24 @@ extern "C" int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, 
     const long long work = (long long)B * F * (Ho / 2) * (Wo / 2);
     SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((frames_to_focus_kernel<T, FrameSrc>), dim3(grid_for(work)), dim3(kBlock), 0, stream,
                                        src, B, F, H, W, Ho, Wo, (typename T::elem*)out_cur, (typename T::elem*)out_sup));
+}
+
+extern "C" int sy_frames_u8_pack_rows(const sy_frame_src* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,
+                                      int dtype, void* stream) {
+    if (rows == nullptr || out_cur == nullptr || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return SY_ERR_ARG;
+    if (dtype != SY_DT_BF16 && dtype != SY_DT_F16 && dtype != SY_DT_F32) return SY_ERR_ARG;
+    if (B > 65535 || (long long)3 * Ho * Wo > (1LL << 30)) return SY_ERR_UNSUPPORTED;      // grid.y; 32-bit per-row indices + stride
+    if (layout == SY_FRAMES_NCHW) {
+        if (dtype != SY_DT_F32) return SY_ERR_ARG;
+        SY_LAUNCH(rows_to_nchw_kernel, rows_grid((long long)3 * Ho * Wo, B), dim3(kBlock), 0, stream, rows, H, W, Ho, Wo,
+                  (float*)out_cur);
+        return SY_LAUNCH_OK() == 0 ? SY_OK : SY_ERR_LAUNCH;
+    }
+    if (layout != SY_FRAMES_FOCUS) return SY_ERR_ARG;
+    if ((Ho & 1) || (Wo & 1)) return SY_ERR_ARG;
+    const dim3 grid = rows_grid((long long)(Ho / 2) * (Wo / 2), B);
+    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((rows_to_focus_kernel<T>), grid, dim3(kBlock), 0, stream, rows, H, W, Ho, Wo,
+                                       (typename T::elem*)out_cur));
 }
 
 extern "C" int sy_resize_bilinear_nchw(const float* in, int N, int C, int H, int W, float* out, int Ho, int Wo,

@@ -12,6 +12,9 @@ Box targets are scaled by the same torch arithmetic as the reference (tiny tenso
 
 There is no CPU implementation here: every entry point needs the HIP library.
 """
+import copy
+
+import numpy as np
 import torch
 
 from . import ops
@@ -84,6 +87,142 @@ class FramePairsU8:
         """Write the stem operand(s) (Focus-packed NHWC16 Views of the plan) straight from the uint8 frames."""
         assert (sup_view is None) == (self.sup is None)
         ops.frames_u8_pack(self.cur, self.sup, self.canvas, self.out_size, cur_view, sup_view, self.decimate, self.mirror)
+
+
+def row_geometry(frame_hw, canvas, decimate=None):
+    """The load-time resize of ONE camera of size frame_hw = (hs, ws) onto the `canvas`, as sy_frames_u8_pack resolves it:
+    -> (decimate, r).  decimate None picks the mode from the size: 1 when the frame is the canvas, 2 when it is exactly twice
+    the canvas, else 0 = `preproc`'s letterbox.  r = min(H / hs, W / ws) is the ratio boxes on the network input are divided by
+    to land on the camera frame (the evaluators' `bboxes /= scale`, exps/evaluators/onex_stream_evaluator.py); None for
+    decimate -1, whose two axes are stretched separately.  ValueError for a geometry the kernel would refuse."""
+    hs, ws = int(frame_hw[0]), int(frame_hw[1])
+    H, W = int(canvas[0]), int(canvas[1])
+    if hs < 1 or ws < 1:
+        raise ValueError("frame size %dx%d" % (hs, ws))
+    if decimate is None:
+        decimate = 1 if (hs, ws) == (H, W) else 2 if (hs, ws) == (2 * H, 2 * W) else 0
+    decimate = int(decimate)
+    if decimate == -1:
+        return -1, None
+    r = min(H / hs, W / ws)
+    if decimate == 0:
+        if int(hs * r) < 1 or int(ws * r) < 1 or int(hs * r) > H or int(ws * r) > W:
+            raise ValueError("a %dx%d frame letterboxed onto %dx%d leaves no pixels (int(h r) x int(w r) = %dx%d)"
+                             % (hs, ws, H, W, int(hs * r), int(ws * r)))
+        return 0, r
+    if decimate not in (1, 2) or hs % decimate or ws % decimate:
+        raise ValueError("decimate %r of a %dx%d frame" % (decimate, hs, ws))
+    h, w = hs // decimate, ws // decimate
+    if h > H or w > W or (h != H and w != W):
+        raise ValueError("decimate %d of a %dx%d frame does not letterbox onto %dx%d with ratio 1" % (decimate, hs, ws, H, W))
+    return decimate, r
+
+
+# sy_frame_src (include/streamyolo_hip.h), one per batch row
+_ROW_DTYPE = np.dtype([("cur", "<u8"), ("Hs", "<i4"), ("Ws", "<i4"), ("row_stride", "<i4"), ("decimate", "<i4"),
+                       ("mirror", "<i4"), ("reserved", "<i4")])
+assert _ROW_DTYPE.itemsize == 32
+
+
+class FrameRowsU8(FramePairsU8):
+    """The per-row counterpart of FramePairsU8 for on_pipe batches (`sup` is always None): every batch row has its OWN camera
+    size, decimate mode and mirror flag, kept as a table of sy_frame_src descriptors the pack kernel reads on the device
+    (sy_frames_u8_pack_rows) — which camera sits in which row is data, so one recorded launch serves every mix.
+
+    Owns a byte staging arena [batch, Hmax * Wmax * 3] on the device (set_row copies a frame contiguously into its row's
+    bytes, row_stride = 3 Ws) and the table with a per-row box divisor behind it: ONE device buffer with pinned host mirrors
+    of the same layout, upload() is a single non-blocking copy.  A row without a frame is the plain 114 canvas.
+
+        rows = FrameRowsU8(batch, (Hmax, Wmax), canvas, device)
+        rows.set_row(0, frame_a); rows.set_row(1, None); rows.upload()
+        model(rows, mode="on_pipe")             # or rows.to_nchw(), rows.pack_focus(view)"""
+
+    def __init__(self, batch, max_frame_hw, canvas, device, out_size=None):
+        self.batch = int(batch)
+        self.max_frame_hw = (int(max_frame_hw[0]), int(max_frame_hw[1]))
+        assert self.batch >= 1 and min(self.max_frame_hw) >= 1
+        self.canvas = (int(canvas[0]), int(canvas[1]))
+        self.out_size = self.canvas if out_size is None else (int(out_size[0]), int(out_size[1]))
+        dev = torch.device(device)
+        B = self.batch
+        self.arena = torch.zeros((B, self.max_frame_hw[0] * self.max_frame_hw[1] * 3), dtype=torch.uint8, device=dev)
+        self._buf = torch.zeros(36 * B, dtype=torch.uint8, device=dev)
+        self.table = self._buf[:32 * B]                              # B sy_frame_src
+        self.divisor = self._buf[32 * B:].view(torch.float32)        # [B]: boxes of row b / divisor[b] = camera coordinates
+        self._rows = np.zeros(B, dtype=_ROW_DTYPE)                   # host master copy, edited by set_row
+        self._div = np.ones(B, dtype=np.float32)
+        # a ring of host mirrors: an upload still in flight keeps reading its mirror while the next tick's rows are written
+        self._ring = [torch.zeros(36 * B, dtype=torch.uint8) for _ in range(4 if dev.type == "cuda" else 1)]
+        if dev.type == "cuda":
+            self._ring = [h.pin_memory() for h in self._ring]
+        self._done = [None] * len(self._ring)
+        self._at = 0
+        # what the plans look at (FramePairsU8's surface): the arena stands for the frames, the table is part of the tape key
+        self.cur, self.sup, self.mirror = self.arena, None, None
+        self.decimate = ("rows", self.table.data_ptr())
+        self.upload()
+
+    def set_row(self, b, frame, mirror=False, decimate=None, divisor=None):
+        """Row b of the next upload() (host table; the pixels go to the arena on the current stream): `frame` uint8 [Hs, Ws, 3]
+        (array or tensor, host or device) or None = no frame.  decimate as FramePairsU8 (None: by size, see row_geometry);
+        divisor: what the row's boxes are divided by (default: the letterbox ratio r).  ValueError — before anything is
+        written — for a frame this object cannot hold or the kernel would refuse."""
+        if not 0 <= b < self.batch:
+            raise ValueError("FrameRowsU8: row %r of %d" % (b, self.batch))
+        if frame is None:
+            self._rows[b] = (0, 0, 0, 0, 1, 0, 0)
+            self._div[b] = 1.0
+            return
+        f = torch.as_tensor(frame)
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
+            raise ValueError("FrameRowsU8: frames must be uint8 [Hs, Ws, 3], got %s %s" % (f.dtype, tuple(f.shape)))
+        hs, ws = int(f.shape[0]), int(f.shape[1])
+        if hs > self.max_frame_hw[0] or ws > self.max_frame_hw[1]:
+            raise ValueError("FrameRowsU8: a %dx%d frame is above max_frame_hw %dx%d" % ((hs, ws) + self.max_frame_hw))
+        dec, r = row_geometry((hs, ws), self.canvas, decimate)
+        if divisor is None:
+            if r is None:
+                raise ValueError("FrameRowsU8: decimate -1 has no single ratio, pass divisor")
+            divisor = r
+        self.arena[b, :hs * ws * 3].view(hs, ws, 3).copy_(f, non_blocking=True)
+        self._rows[b] = (self.arena.data_ptr() + b * self.arena.stride(0), hs, ws, ws * 3, dec, 1 if mirror else 0, 0)
+        self._div[b] = divisor
+
+    def upload(self):
+        """The rows as set_row left them -> the device table: ONE non-blocking copy on the current stream."""
+        self._at = (self._at + 1) % len(self._ring)
+        if self._done[self._at] is not None:
+            self._done[self._at].synchronize()                       # (only when the device is a whole ring of ticks behind)
+        host = self._ring[self._at].numpy()
+        B = self.batch
+        host[:32 * B] = self._rows.view(np.uint8)
+        host[32 * B:] = self._div.view(np.uint8)
+        self._buf.copy_(self._ring[self._at], non_blocking=True)
+        if self._buf.is_cuda:
+            ev = self._done[self._at] or torch.cuda.Event()
+            ev.record()
+            self._done[self._at] = ev
+
+    # ---- FramePairsU8's surface ----------------------------------------------------------------------------
+    def resized(self, tsize):
+        """Same rows (shared arena and table), run at `tsize`."""
+        other = copy.copy(self)
+        other.out_size = (int(tsize[0]), int(tsize[1]))
+        return other
+
+    def paired_with_self(self):
+        raise ValueError("FrameRowsU8 is an on_pipe input (one frame per row)")
+
+    def to_nchw(self):
+        """fp32 [batch, 3, Ho, Wo] of the rows last uploaded."""
+        out = torch.empty(tuple(self.shape), dtype=torch.float32, device=self.device)
+        ops.frames_u8_pack_rows(self.table, self.batch, self.canvas, self.out_size, out)
+        return out
+
+    def pack_focus(self, cur_view, sup_view=None):
+        """Write the stem operand (Focus-packed NHWC16 View of the plan) straight from the rows last uploaded."""
+        assert sup_view is None
+        ops.frames_u8_pack_rows(self.table, self.batch, self.canvas, self.out_size, cur_view)
 
 
 def preprocess(inputs, targets, tsize, input_size):

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .data import FramePairsU8
+from .data import FramePairsU8, FrameRowsU8, row_geometry
 from .postprocess import postprocess_device
 
 
@@ -120,12 +120,30 @@ class MultiStreamDetector:
         a, b = det.open(), det.open()
         (boxes_a, scores_a, labels_a, _), (boxes_b, scores_b, labels_b, _) = det([frame_a, frame_b], [a, b])
 
-    All streams share one frame size.  Which frames go into a tick is the caller's scheduling policy."""
+    Without `max_frame_hw` all streams share the one frame size `frame_hw`.  With max_frame_hw=(Hmax, Wmax) the detector runs
+    in mixed mode: open(frame_hw=(h, w)) fixes a stream's own camera size for its lifetime, and cameras of different
+    resolutions share the ticks — every batch row is the same canvas-sized network input, and the pack kernel reads each row's
+    size, resize mode and pixels from a device table (sy_frames_u8_pack_rows, data.FrameRowsU8), so the mix is data too and
+    the tape stays the one tape.  A stream opened with a size is letterboxed the way `preproc` does it (a frame of the canvas
+    size is copied, one of exactly twice the canvas decimated 2x, any other resized by r = min(H / h, W / w) onto the 114
+    canvas) and its boxes are divided by that r, as the evaluators do; a stream opened without one is a `frame_hw` camera
+    treated exactly as in the uniform mode.
+
+        det = MultiStreamDetector(model, (1200, 1920), max_streams=16, batch=8, max_frame_hw=(2048, 2048)); det.warm_up()
+        ring, side = det.open(), det.open(frame_hw=(1550, 2048))
+        (boxes_r, ...), (boxes_s, ...) = det([ring_frame, side_frame], [ring, side])
+
+    Which frames go into a tick is the caller's scheduling policy."""
 
     def __init__(self, model, frame_hw, max_streams=16, batch=8, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65,
-                 dtype="fp16", device="cuda"):
+                 dtype="fp16", device="cuda", max_frame_hw=None):
         if int(batch) < 1 or int(max_streams) < 1:
             raise ValueError("MultiStreamDetector: batch and max_streams must be positive")
+        if max_frame_hw is not None:
+            max_frame_hw = (int(max_frame_hw[0]), int(max_frame_hw[1]))
+            if max_frame_hw[0] < int(frame_hw[0]) or max_frame_hw[1] < int(frame_hw[1]):
+                raise ValueError("MultiStreamDetector: max_frame_hw %r is below frame_hw %r" % (max_frame_hw, tuple(frame_hw)))
+        self.max_frame_hw = max_frame_hw
         self.model = model.to(device).eval().set_compute_dtype(dtype)
         self.device = torch.device(device)
         self.in_scale, self.batch, self.max_streams = in_scale, int(batch), int(max_streams)
@@ -141,9 +159,15 @@ class MultiStreamDetector:
         else:
             self.decimate = -1
         self.num_classes, self.conf_thre, self.nms_thresh = num_classes, conf_thre, nms_thresh
-        # detector-owned staging: row b of a tick's frames (rows without a frame keep stale pixels; their outputs are ignored)
-        self._stage = torch.zeros((self.batch,) + self.frame_hw + (3,), dtype=torch.uint8, device=self.device)
-        self._in = FramePairsU8(self._stage, None, self.canvas, self.decimate)
+        if self.max_frame_hw is None:
+            # detector-owned staging: row b of a tick's frames (rows without a frame keep stale pixels; their outputs are ignored)
+            self._stage = torch.zeros((self.batch,) + self.frame_hw + (3,), dtype=torch.uint8, device=self.device)
+            self._in = FramePairsU8(self._stage, None, self.canvas, self.decimate)
+        else:
+            # mixed mode: a byte arena per row and the per-row descriptor table (rows without a frame are the plain canvas)
+            self._stage = None
+            self._in = FrameRowsU8(self.batch, self.max_frame_hw, self.canvas, self.device)
+        self._geom = {}                                          # mixed mode: open stream id -> (frame hw, decimate, box divisor)
         split_k = str(dtype) not in ("fp32", "torch.float32") and os.environ.get("STREAMYOLO_STREAM_SPLITK", "1") != "0"
         self.plan = model._plans.inference(model.backbone, model.head, "on_pipe", self._in, owner=model, split_k=split_k)
         from .engine import StreamSlots
@@ -156,14 +180,25 @@ class MultiStreamDetector:
         self._next_id = 0                                        # ids are never reused: a closed id stays invalid
 
     # ---- stream bookkeeping (host side only) --------------------------------------------------------------------
-    def open(self):
-        """A new stream: its id.  Its first frame fuses with itself (`buffer = None`, streamyolo_det.py:150)."""
+    def open(self, frame_hw=None):
+        """A new stream: its id.  Its first frame fuses with itself (`buffer = None`, streamyolo_det.py:150).  Mixed mode:
+        frame_hw = (h, w) is this stream's camera size for its lifetime (None: the detector's frame_hw and in_scale)."""
+        geom = (self.frame_hw, self.decimate, self.in_scale)
+        if frame_hw is not None:
+            if self.max_frame_hw is None:
+                raise ValueError("MultiStreamDetector: open(frame_hw=...) needs a detector built with max_frame_hw")
+            hw = (int(frame_hw[0]), int(frame_hw[1]))
+            if hw[0] > self.max_frame_hw[0] or hw[1] > self.max_frame_hw[1]:
+                raise ValueError("MultiStreamDetector: a %dx%d camera is above max_frame_hw %dx%d" % (hw + self.max_frame_hw))
+            decimate, r = row_geometry(hw, self.canvas)          # (ValueError: nothing of the frame is left on the canvas)
+            geom = (hw, decimate, r)
         if not self._free:
             raise RuntimeError("MultiStreamDetector: all %d streams are open" % self.max_streams)
         sid = self._next_id
         self._next_id += 1
         self._slot_of[sid] = self._free.pop(0)
         self._first[sid] = True
+        self._geom[sid] = geom
         return sid
 
     def _known(self, sid):
@@ -181,11 +216,17 @@ class MultiStreamDetector:
         self._free.append(self._slot_of.pop(sid))
         self._free.sort()
         del self._first[sid]
+        del self._geom[sid]
 
     def warm_up(self, n=10):
         """streamyolo_det.py:113-120 on a dummy batch (no row carries a frame: no stream's state is written); builds, tunes and
         records the plan.  Afterwards every open stream starts a new sequence."""
-        self._stage.fill_(1)
+        if self._stage is not None:
+            self._stage.fill_(1)
+        else:
+            for b in range(self.batch):
+                self._in.set_row(b, None)
+            self._in.upload()
         self.state.set_rows((), ())
         self.state.upload()
         with torch.no_grad():
@@ -200,25 +241,35 @@ class MultiStreamDetector:
         """Everything that can be wrong with a call, found BEFORE anything is written."""
         if len(frames) != len(sids):
             raise ValueError("MultiStreamDetector: %d frames for %d stream ids" % (len(frames), len(sids)))
-        fs = []
-        for f in frames:
-            f = torch.as_tensor(f)
-            if f.dtype != torch.uint8 or tuple(f.shape) != self.frame_hw + (3,):
-                raise ValueError("MultiStreamDetector: frames must be uint8 [%d, %d, 3], got %s %s"
-                                 % (self.frame_hw + (f.dtype, tuple(f.shape))))
-            fs.append(f)
         for t0 in range(0, len(sids), self.batch):
             tick = list(sids[t0:t0 + self.batch])
             for sid in tick:
                 self._known(sid)
             if len(set(tick)) != len(tick):
                 raise ValueError("MultiStreamDetector: a stream id appears twice in one tick: %r" % (tick,))
+        fs = []
+        for f, sid in zip(frames, sids):
+            f = torch.as_tensor(f)
+            hw = self._geom[sid][0]                              # its stream's camera size (uniform mode: frame_hw)
+            if f.dtype != torch.uint8 or tuple(f.shape) != hw + (3,):
+                raise ValueError("MultiStreamDetector: frames of stream %r must be uint8 [%d, %d, 3], got %s %s"
+                                 % ((sid,) + hw + (f.dtype, tuple(f.shape))))
+            fs.append(f)
         return fs
 
     def _tick(self, frames, sids):
         n = len(sids)
-        for b, f in enumerate(frames):
-            self._stage[b].copy_(f, non_blocking=True)
+        if self._stage is not None:
+            for b, f in enumerate(frames):
+                self._stage[b].copy_(f, non_blocking=True)
+        else:
+            for b in range(self.batch):
+                if b < n:
+                    _, decimate, div = self._geom[sids[b]]
+                    self._in.set_row(b, frames[b], decimate=decimate, divisor=div)
+                else:
+                    self._in.set_row(b, None)
+            self._in.upload()
         self.state.set_rows([self._slot_of[s] for s in sids], [self._first[s] for s in sids])
         self.state.upload()
         for s in sids:
@@ -231,10 +282,13 @@ class MultiStreamDetector:
         """One tick (len(frames) <= batch) without any host read: (det [batch, A, 7], cnt [batch], rows) — rows 0..rows-1 of
         the device tensors belong to `sids` in order (kept detections det[b, :cnt[b]]: x1, y1, x2, y2 on the network input,
         obj, class_conf, class), the other rows are meaningless.  The tensors are detector-owned and overwritten by the next
-        tick.  Frames are copied into the staging tensor, the tables go up in one non-blocking copy from pinned memory."""
+        tick.  Frames are copied into the staging tensor, the tables go up in one non-blocking copy from pinned memory.
+        Mixed mode returns a fourth value: the device tensor div [batch] (float32, detector-owned) — the boxes of row b divided
+        by div[b] are in that stream's camera coordinates (what __call__ does on the host)."""
         if len(sids) > self.batch:
             raise ValueError("MultiStreamDetector: %d frames in one tick of batch %d" % (len(sids), self.batch))
-        return self._tick(self._check(frames, sids), list(sids))
+        res = self._tick(self._check(frames, sids), list(sids))
+        return res if self._stage is not None else res + (self._in.divisor,)
 
     def __call__(self, frames, sids):
         """n camera frames (uint8 [H, W, 3] arrays or tensors) and the ids of their streams -> n (bboxes, scores, labels, None)
@@ -248,7 +302,7 @@ class MultiStreamDetector:
             rows = det[:n, :max(int(counts.max()), 1)].cpu().numpy()
             for b in range(n):
                 d = rows[b, :int(counts[b])]
-                res.append((d[:, :4] / self.in_scale, d[:, 4] * d[:, 5], d[:, 6].astype(np.int32), None))
+                res.append((d[:, :4] / self._geom[sids[t0 + b]][2], d[:, 4] * d[:, 5], d[:, 6].astype(np.int32), None))
         return res
 
 

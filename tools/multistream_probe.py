@@ -10,6 +10,12 @@ yardstick; the best round counts.  Prints one JSON line (and writes it to --out)
 
     python tools/multistream_probe.py --out profiles/r08/multistream_probe.json
     python tools/multistream_probe.py --trace 8      # only warm up batch 8 and run 20 ticks (for rocprofv3 --kernel-trace --stats)
+    python tools/multistream_probe.py --mixed 1 --batches 1,4,8 --out profiles/r08/multistream_probe_mixed.json
+
+--mixed 1: the detector runs in mixed mode (max_frame_hw) and the rows' cameras cycle through three sizes — the frame size
+(2x decimation), the network input size (copy) and 3/4 x 5/6 of the frame (`preproc`'s letterbox, r = 0.6 for 1200x1920) — all
+packed by the ONE sy_frames_u8_pack_rows launch of the tape.  Every row of the result also carries the uniform detector's tick
+at the same batch, measured in the same process, alternating (`uniform_ms_per_tick`, `mixed_over_uniform`).
 """
 import argparse
 import json
@@ -35,6 +41,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace", type=int, default=0, help="batch: warm up, run 20 ticks of that batch and exit (profiler runs)")
     ap.add_argument("--baseline-only", type=int, default=0, help="1: only the single-camera yardstick (also runs on older trees)")
+    ap.add_argument("--mixed", type=int, default=0, help="1: mixed-mode detector, row cameras cycling through three sizes")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -96,6 +103,12 @@ def main():
     res = {"tool": "multistream_probe", "model": args.model, "dtype": args.dtype, "frame": list(hw), "ticks": args.ticks,
            "warmup": args.warmup, "rounds": args.rounds, "kernel_source_key": _lib.kernel_source_key(),
            "device": torch.cuda.get_device_name(0), "rows": []}
+    # --mixed: camera i has size sizes[i % 3]; its pictures are the frame itself, every second pixel of it, its top-left part
+    sizes = [hw, (hw[0] // 2, hw[1] // 2), (hw[0] * 3 // 4, hw[1] * 5 // 6)]
+    if args.mixed:
+        res["mixed_sizes"] = [list(v) for v in sizes]
+        mixed_frames = [(raw[i], raw[i][::2, ::2].contiguous(), raw[i][:sizes[2][0], :sizes[2][1]].contiguous())[i % 3]
+                        for i in range(nmax)]
 
     def emit():
         line = json.dumps(res)
@@ -116,28 +129,45 @@ def main():
     from streamyolo_amd.streaming import MultiStreamDetector
     single_tick(1)                                               # (steady state: the tape is recorded)
     for B in ([args.trace] if args.trace else batches):
-        det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
-        det.warm_up(args.warmup)
-        sids = [det.open() for _ in range(B)]
-        det.detect_device(frames[:B], sids)                      # first rows done: steady state
+        uni = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+        uni.warm_up(args.warmup)
+        uni_sids = [uni.open() for _ in range(B)]
+        uni.detect_device(frames[:B], uni_sids)                  # first rows done: steady state
+        det, sids, tick_frames = uni, uni_sids, frames
+        if args.mixed:
+            det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev, max_frame_hw=hw)
+            det.warm_up(args.warmup)
+            sids = [det.open(frame_hw=sizes[i % 3]) for i in range(B)]
+            tick_frames = mixed_frames
+            det.detect_device(tick_frames[:B], sids)
         for n in ([B] if (B != 8 or args.trace) else sorted(set([int(v) for v in args.active.split(",") if v] + [B]))):
             def multi_tick():
-                det.detect_device(frames[:n], sids[:n])
+                det.detect_device(tick_frames[:n], sids[:n])
+
+            def uniform_tick():
+                uni.detect_device(frames[:n], uni_sids[:n])
             if args.trace:
                 timed(multi_tick, 20)
                 print(json.dumps({"traced_batch": B, "ticks": 20}))
                 return
             multi_tick()
-            best_m, best_s, host_m = float("inf"), float("inf"), float("inf")
+            best_m, best_s, host_m, best_u = float("inf"), float("inf"), float("inf"), float("inf")
             for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
-                m, h = timed(multi_tick, args.ticks)
+                if args.mixed:
+                    multi_tick()                                 # (two detectors of one batch share the plan: the untimed tick
+                m, h = timed(multi_tick, args.ticks)             #  after a switch re-records its tape)
+                if args.mixed:
+                    uniform_tick()
+                    best_u = min(best_u, timed(uniform_tick, args.ticks)[0])
                 s, _ = timed(lambda: single_tick(n), args.ticks)
                 best_m, best_s, host_m = min(best_m, m), min(best_s, s), min(host_m, h)
             res["rows"].append({"batch": B, "active": n, "ms_per_tick": best_m, "frames_per_s": 1e3 * n / best_m,
                                 "host_ms_per_tick": host_m, "single_ms_per_tick": best_s,
                                 "single_frames_per_s": 1e3 * n / best_s, "tick_over_n_single_frames": best_m / best_s})
+            if args.mixed:
+                res["rows"][-1].update({"mixed": True, "uniform_ms_per_tick": best_u, "mixed_over_uniform": best_m / best_u})
             emit()
-        del det                                                  # (its plan and pools go back to the allocator)
+        del det, uni                                             # (their plans and pools go back to the allocator)
     print(emit())
 
 
