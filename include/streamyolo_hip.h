@@ -179,20 +179,44 @@ SY_API int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, int 
                              int row_stride, int decimate, const uint8_t* mirror, int H, int W, int Ho, int Wo,
                              int layout, void* out_cur, void* out_sup, int dtype, void* stream);
 
+/* sy_frames_u8_pack for frames in another pixel format (sy_frames_u8_pack itself = SY_PIX_BGR).  For every format the
+ * output is bit for bit what sy_frames_u8_pack writes for the frame first converted to uint8 [Hs, Ws, 3] BGR: the conversion
+ * happens per SOURCE pixel, before any decimation or bilinear tap — what cv2.cvtColor in front of the reference's loop does.
+ *   SY_PIX_RGB   [B, Hs, Ws, 3] as BGR, channel c of the converted frame = byte 2 - c (PIL, torchvision, GStreamer).
+ *   SY_PIX_NV12  what hardware video decoders deliver: cur / sup are [B] images of Hs * 3 / 2 rows of ONE pitch
+ *                (row_stride >= Ws bytes): Hs rows of luma, then — starting at row Hs — Hs / 2 rows of interleaved chroma
+ *                (U, V): the [Hs * 3 / 2, Ws] array cv2.cvtColor(.., COLOR_YUV2BGR_NV12) takes, with an optional pitch.
+ *                Surfaces whose chroma plane starts elsewhere (a padded luma height, a detached plane) are NOT supported.
+ *                Hs and Ws even (else SY_ERR_UNSUPPORTED); image_stride >= row_stride * Hs * 3 / 2 (else SY_ERR_ARG).
+ *                Chroma of pixel (y, x) = the pair at chroma row y >> 1, byte 2 * (x >> 1): nearest, no interpolation.
+ *                BT.601 limited range in int32 fixed point, as OpenCV publishes it for COLOR_YUV2BGR_NV12 (restated from
+ *                published source, unpinned against a cv2 binary):
+ *                    y' = max(Y - 16, 0), u = U - 128, v = V - 128
+ *                    B = sat8((1220542 y' + 2116026 u            + (1 << 19)) >> 20)
+ *                    G = sat8((1220542 y' -  409993 u - 852492 v + (1 << 19)) >> 20)
+ *                    R = sat8((1220542 y' + 1673527 v            + (1 << 19)) >> 20)
+ * Reads stay inside Hs (NV12: Hs * 3 / 2) rows of row_stride bytes.  An unknown format: SY_ERR_ARG. */
+enum { SY_PIX_BGR = 0, SY_PIX_RGB = 1, SY_PIX_NV12 = 2 };
+SY_API int sy_frames_u8_pack_fmt(const uint8_t* cur, const uint8_t* sup, int B, int Hs, int Ws, int64_t image_stride,
+                                 int row_stride, int decimate, const uint8_t* mirror, int H, int W, int Ho, int Wo,
+                                 int layout, void* out_cur, void* out_sup, int dtype, int format, void* stream);
+
 /* The same pipeline with one frame source PER BATCH ROW, read on the device: cameras of different resolutions in one batch
  * (MultiStreamDetector's mixed mode).  rows: B descriptors in DEVICE memory; row b of out_cur is bit for bit what
  * sy_frames_u8_pack writes for that frame alone (same Hs, Ws, decimate, mirror, H, W, Ho, Wo, layout, dtype; sup = NULL).
  * ONE launch whose grid depends on (B, Ho, Wo, layout) only, so a recorded launch serves any table contents.  A row with
  * cur == NULL or Hs == 0 has no frame: the plain 114 canvas, nothing is read.  The host cannot see the table: the caller
- * validates it (every frame addressable for Hs rows of row_stride >= 3 Ws bytes; decimate as above); a descriptor that
- * sy_frames_u8_pack would refuse is written as a row without a frame, never read through.
+ * validates it (every frame addressable for Hs rows of row_stride >= 3 Ws bytes — SY_PIX_NV12: Hs * 3 / 2 rows of
+ * row_stride >= Ws bytes; decimate as above); a descriptor that sy_frames_u8_pack_fmt would refuse (an unknown format and an
+ * odd NV12 size included) is written as a row without a frame, never read through.  The format is per-row data like the size:
+ * cameras of different formats share one launch.
  * layout SY_FRAMES_NCHW: out_cur = fp32 [B, 3, Ho, Wo] (dtype = SY_DT_F32); SY_FRAMES_FOCUS: [B, Ho/2, Wo/2, 16] of `dtype`. */
 typedef struct sy_frame_src {      /* 32 bytes */
-    const uint8_t* cur;            /* [Hs, Ws, 3] BGR; NULL or Hs == 0: the row has no frame */
+    const uint8_t* cur;            /* [Hs, Ws, 3] BGR / RGB or NV12 [Hs * 3 / 2, Ws]; NULL or Hs == 0: the row has no frame */
     int32_t Hs, Ws, row_stride;    /* row_stride in bytes */
     int32_t decimate;              /* 1 | 2 | 0 | -1, exactly as sy_frames_u8_pack */
     int32_t mirror;                /* != 0: image[:, ::-1] */
-    int32_t reserved;
+    int32_t format;                /* SY_PIX_*; 0 = BGR (the field was `reserved`, always 0) */
 } sy_frame_src;
 SY_API int sy_frames_u8_pack_rows(const sy_frame_src* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,
                                   int dtype, void* stream);

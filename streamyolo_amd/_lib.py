@@ -21,6 +21,16 @@ CONV_FWD, CONV_DGRAD = 0, 1
 ABI_VERSION = 7          # SY_ABI_VERSION of include/streamyolo_hip.h this binding was written against
 _ERR = {1: "bad argument", 2: "kernel launch failed", 3: "unsupported shape"}
 SY_ERR_UNSUPPORTED = 3
+PIX_BGR, PIX_RGB, PIX_NV12 = 0, 1, 2          # SY_PIX_* of include/streamyolo_hip.h
+PIXEL_FORMATS = {"bgr": PIX_BGR, "rgb": PIX_RGB, "nv12": PIX_NV12}
+
+
+def pixel_format_code(pixel_format):
+    """"bgr" | "rgb" | "nv12" -> SY_PIX_*; ValueError for anything else."""
+    try:
+        return PIXEL_FORMATS[pixel_format]
+    except (KeyError, TypeError):
+        raise ValueError("pixel_format must be one of %s, got %r" % (sorted(PIXEL_FORMATS), pixel_format)) from None
 
 
 class HipLibraryError(RuntimeError):
@@ -74,7 +84,7 @@ class OptimEntry(C.Structure):
 class FrameSrc(C.Structure):
     """sy_frame_src (include/streamyolo_hip.h): 32 bytes of DEVICE memory per batch row."""
     _fields_ = [("cur", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("row_stride", C.c_int32),
-                ("decimate", C.c_int32), ("mirror", C.c_int32), ("reserved", C.c_int32)]
+                ("decimate", C.c_int32), ("mirror", C.c_int32), ("format", C.c_int32)]
 
 
 class StreamLevel(C.Structure):
@@ -112,6 +122,7 @@ SIGNATURES = {
     "sy_conv2d_wgrad": (_I, [C.POINTER(WgradDesc), _P]),
     "sy_focus_pack": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sy_frames_u8_pack": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "sy_frames_u8_pack_fmt": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
     "sy_frames_u8_pack_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sy_resize_bilinear_nchw": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "sy_resize_nearest": (_I, [_P, _I, _I, _I, _I, _I, _L, _P, _I, _I, _I, _L, _I, _P]),

@@ -22,6 +22,24 @@
 //                coordinate fx = (float)((dx + 0.5) * scale - 0.5), taps sx = floor(fx), sx + 1 (horizontally: clamped at the
 //                borders with the fraction zeroed; vertically: row indices clamped, fraction kept), coefficients saturate_cast<short>(frac * 2048) (round half to even), horizontal pass
 //                in int32, vertical pass ((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2.
+//
+// Pixel formats (sy_frames_u8_pack_fmt, sy_frame_src.format).  Frames are BGR as cv2.imread delivers them; a deployment gets RGB
+// (PIL, torchvision, GStreamer) or NV12 (hardware video decoders) and would convert on the CPU first.  Here the conversion is part
+// of the same launch, per SOURCE pixel and before any decimation or bilinear tap: for every format the output is bit for bit what
+// the BGR path writes for the converted uint8 [Hs, Ws, 3] frame.  The BGR kernels are the ones they were (frame_at, sample and
+// focus_pixel keep their expressions); RGB reads byte 2 - c; NV12 has kernels of its own that form the (B, G, R) triple of a source
+// pixel ONCE (the other paths call sample() once per channel).
+//   NV12 layout  ONE pitch for both planes: Hs rows of luma, then — starting at row Hs — Hs / 2 rows of interleaved chroma (U, V):
+//                the [Hs * 3 / 2, Ws] array cv2.cvtColor takes, with an optional pitch; Hs, Ws even.  Chroma of pixel (y, x) = the
+//                pair at chroma row y >> 1, byte 2 * (x >> 1) (nearest).  Surfaces whose chroma plane starts elsewhere (a padded
+//                luma height, a detached plane) are out of scope.
+//   arithmetic   BT.601 limited range in the int32 fixed point OpenCV publishes for COLOR_YUV2BGR_NV12 (nv12_bgr below) — like the
+//                resize arithmetic restated from published source, PARITY UNPINNED against a cv2 binary.
+//   fast path    NV12 -> Focus layout without the canvas resize, decimate 1 | 2 (1200x1920 -> 600x960 is this case): one thread
+//                owns one Focus pixel = 2x2 output pixels; decimate 2: a 4x4 luma block and 2x2 chroma pairs in six 32-bit loads
+//                (decimate 1: 2x2 luma, one pair, three 16-bit loads) instead of 24 single-byte loads.  Taken — per launch, per
+//                row in the rows kernel — only when base pointers, pitch and image stride are multiples of the load width and ws is
+//                even; a Focus pixel not wholly inside the image takes the generic path.  Bit-identical with the generic path.
 #include "sy_pointwise.h"
 
 namespace {
@@ -106,6 +124,112 @@ __device__ __forceinline__ float frame_at(const unsigned char* p, const FrameGeo
     return (float)(((int)r0[0] + (int)r0[3] + (int)r1[0] + (int)r1[3] + 2) >> 2);
 }
 
+// ---- NV12 (see the header): BT.601 limited range, int32 fixed point with 20 fractional bits.  No intermediate leaves int32:
+// |1220542 y'| <= 2.92e8, the chroma terms with the rounding constant are within [-1.62e8, 2.70e8].
+struct Chroma { int b, g, r; };         // the chroma terms of B, G, R with the rounding constant: once per (U, V) pair
+__device__ __forceinline__ Chroma nv12_chroma(int U, int V) {
+    const int u = U - 128, v = V - 128;
+    Chroma k;
+    k.b = 2116026 * u + (1 << 19);
+    k.g = -409993 * u - 852492 * v + (1 << 19);
+    k.r = 1673527 * v + (1 << 19);
+    return k;
+}
+__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+__device__ __forceinline__ void nv12_bgr(int Y, const Chroma& k, int o[3]) {
+    const int y = 1220542 * (Y - 16 < 0 ? 0 : Y - 16);
+    o[0] = sat8((y + k.b) >> 20);
+    o[1] = sat8((y + k.g) >> 20);
+    o[2] = sat8((y + k.r) >> 20);
+}
+// (B, G, R) of source pixel (sy, sx) of the NV12 image at p: luma row sy, chroma row src_h + (sy >> 1), pair 2 * (sx >> 1)
+__device__ __forceinline__ void nv12_px(const unsigned char* p, const FrameGeom& g, int sy, int sx, int o[3]) {
+    const unsigned char* uv = p + (long long)(g.src_h + (sy >> 1)) * g.row_stride + 2 * (sx >> 1);
+    nv12_bgr((int)p[(long long)sy * g.row_stride + sx], nv12_chroma((int)uv[0], (int)uv[1]), o);
+}
+
+// frame_at for an NV12 image, all three channels of canvas pixel (y, x) at once: every source pixel is converted once and the
+// integer arithmetic of frame_at runs on the triples.  Reads stay inside src_h * 3 / 2 rows of src_w <= row_stride bytes.
+__device__ __forceinline__ void frame_at3_nv12(const unsigned char* p, const FrameGeom& g, bool mirror, int y, int x, float o[3]) {
+    if (y >= g.hs || x >= g.ws) { o[0] = 114.0f; o[1] = 114.0f; o[2] = 114.0f; return; }
+    if (mirror) x = g.ws - 1 - x;
+    if (g.dec == 1) {
+        int a[3];
+        nv12_px(p, g, y, x, a);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = (float)a[c];
+        return;
+    }
+    if (g.dec == 0) {
+        const Tap ty = frame_tap<false>(y, g.scale_y, g.src_h), tx = frame_tap<true>(x, g.scale_x, g.src_w);
+        int p00[3], p01[3], p10[3], p11[3];
+        nv12_px(p, g, ty.s0, tx.s0, p00); nv12_px(p, g, ty.s0, tx.s1, p01);
+        nv12_px(p, g, ty.s1, tx.s0, p10); nv12_px(p, g, ty.s1, tx.s1, p11);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int S0 = p00[c] * tx.a0 + p01[c] * tx.a1;                              // horizontal pass, scaled by 2^11
+            const int S1 = p10[c] * tx.a0 + p11[c] * tx.a1;
+            const int v = (((ty.a0 * (S0 >> 4)) >> 16) + ((ty.a1 * (S1 >> 4)) >> 16) + 2) >> 2;
+            o[c] = (float)(v < 0 ? 0 : (v > 255 ? 255 : v));
+        }
+        return;
+    }
+    // the 2x2 source block of an exact 2x decimation shares one chroma pair: chroma row y, pair 2 x
+    const unsigned char* r0 = p + (long long)(2 * y) * g.row_stride + 2 * x;
+    const unsigned char* r1 = r0 + g.row_stride;
+    const unsigned char* uv = p + (long long)(g.src_h + y) * g.row_stride + 2 * x;
+    const Chroma k = nv12_chroma((int)uv[0], (int)uv[1]);
+    int a[3], b[3], c_[3], d[3];
+    nv12_bgr((int)r0[0], k, a); nv12_bgr((int)r0[1], k, b); nv12_bgr((int)r1[0], k, c_); nv12_bgr((int)r1[1], k, d);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = (float)((a[c] + b[c] + c_[c] + d[c] + 2) >> 2);
+}
+
+// 16 / 32 bits at an address that is a multiple of the width (the fast path's precondition)
+__device__ __forceinline__ unsigned load_u16(const unsigned char* p) { return *reinterpret_cast<const unsigned short*>(p); }
+__device__ __forceinline__ unsigned load_u32(const unsigned char* p) { return *reinterpret_cast<const unsigned int*>(p); }
+
+// The NV12 fast path: the Focus pixel (h2, w2) = output pixels (2 h2 + i, 2 w2 + j) of an image it lies wholly inside (2 h2 + 1
+// < hs, 2 w2 + 1 < ws), dec 1 | 2, ws even, p and row_stride multiples of 2 (dec 1) / 4 (dec 2) -> px[i][j][c], j counted in
+// IMAGE order (mirrored: output column 2 w2 + j is px[.][1 - j] — the caller selects, so that every index here is a constant
+// and the block stays in registers).  The same integers as frame_at3_nv12 from wide loads.
+__device__ __forceinline__ void nv12_focus_block(const unsigned char* p, const FrameGeom& g, bool mirror, int h2, int w2,
+                                                 int px[2][2][3]) {
+    const int xs = mirror ? g.ws - 2 - 2 * w2 : 2 * w2;             // the pair's left column in the (unmirrored) image: even
+    if (g.dec == 1) {
+        const unsigned uv = load_u16(p + (long long)(g.src_h + h2) * g.row_stride + xs);
+        const Chroma k = nv12_chroma((int)(uv & 255u), (int)(uv >> 8));
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const unsigned l = load_u16(p + (long long)(2 * h2 + i) * g.row_stride + xs);
+            nv12_bgr((int)(l & 255u), k, px[i][0]);
+            nv12_bgr((int)(l >> 8), k, px[i][1]);
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        // output row 2 h2 + i: luma rows 4 h2 + 2 i and the next, chroma row 2 h2 + i; bytes 2 xs .. 2 xs + 3 of each
+        const unsigned char* r0 = p + (long long)(4 * h2 + 2 * i) * g.row_stride + 2 * xs;
+        const unsigned l0 = load_u32(r0), l1 = load_u32(r0 + g.row_stride);
+        const unsigned uv = load_u32(p + (long long)(g.src_h + 2 * h2 + i) * g.row_stride + 2 * xs);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {                               // image column xs + j
+            const Chroma k = nv12_chroma((int)((uv >> (16 * j)) & 255u), (int)((uv >> (16 * j + 8)) & 255u));
+            int a[3], b[3], c_[3], d[3];
+            nv12_bgr((int)((l0 >> (16 * j)) & 255u), k, a); nv12_bgr((int)((l0 >> (16 * j + 8)) & 255u), k, b);
+            nv12_bgr((int)((l1 >> (16 * j)) & 255u), k, c_); nv12_bgr((int)((l1 >> (16 * j + 8)) & 255u), k, d);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) px[i][j][c] = (a[c] + b[c] + c_[c] + d[c] + 2) >> 2;
+        }
+    }
+}
+// what the fast path needs of an image besides dec 1 | 2: even ws and every row start a multiple of the load width
+__host__ __device__ inline bool nv12_fast_ok(const FrameGeom& g, unsigned long long addr_bits) {
+    if ((g.dec != 1 && g.dec != 2) || (g.ws & 1)) return false;
+    return ((addr_bits | (unsigned long long)g.row_stride) & (g.dec == 2 ? 3ull : 1ull)) == 0;
+}
+
 struct FrameSrc {               // uint8 HWC frames of one batch, one geometry: current and (optional) support
     const unsigned char* img[2];
     long long image_stride;     // bytes between images
@@ -118,25 +242,49 @@ struct FrameSrc {               // uint8 HWC frames of one batch, one geometry: 
     }
 };
 
+struct FrameSrcRGB : FrameSrc {  // the same frames in RGB order
+    __device__ __forceinline__ float at(int n, int f, int c, int y, int x) const { return FrameSrc::at(n, f, 2 - c, y, x); }
+};
+struct FrameSrcNV12 : FrameSrc { // [B] NV12 images of src_h * 3 / 2 rows
+    __device__ __forceinline__ const unsigned char* image(int n, int f) const { return img[f] + n * image_stride; }
+    __device__ __forceinline__ bool mirrored(int n) const { return mirror != nullptr && mirror[n]; }
+    __device__ __forceinline__ void at3(int n, int f, int y, int x, float o[3]) const {
+        if (y >= g.hs || x >= g.ws) { o[0] = 114.0f; o[1] = 114.0f; o[2] = 114.0f; return; }
+        frame_at3_nv12(image(n, f), g, mirrored(n), y, x, o);
+    }
+};
+
 // One batch row of sy_frames_u8_pack_rows: its descriptor, resolved.  A row without a frame — or with a descriptor no frame can
 // have (the host cannot see the table: the caller validates it) — has hs = ws = 0: the plain 114 canvas, nothing is read.
 struct RowSrc {
     const unsigned char* p;
     FrameGeom g;
     bool mirror;
+    int fmt;                    // SY_PIX_*: scalar, like g.dec
+    bool fast;                  // NV12: the image qualifies for the fast path (nv12_fast_ok)
     __device__ __forceinline__ RowSrc(const sy_frame_src* rows, int b, int H, int W) {
         const sy_frame_src d = rows[b];                         // one 32-byte load per workgroup (b = blockIdx.y: uniform)
-        p = nullptr; mirror = false;
+        p = nullptr; mirror = false; fmt = SY_PIX_BGR; fast = false;
         g.row_stride = 0; g.hs = 0; g.ws = 0; g.dec = 1; g.src_h = 0; g.src_w = 0; g.scale_y = 1.0; g.scale_x = 1.0;
         if (d.cur == nullptr || d.Hs <= 0 || d.Ws <= 0 || d.decimate < -1 || d.decimate > 2) return;
-        if ((d.decimate == 2 && ((d.Hs & 1) || (d.Ws & 1))) || (long long)d.row_stride < (long long)d.Ws * 3) return;
+        if (d.format != SY_PIX_BGR && d.format != SY_PIX_RGB && d.format != SY_PIX_NV12) return;
+        const bool nv12 = d.format == SY_PIX_NV12;
+        if ((d.decimate == 2 || nv12) && ((d.Hs & 1) || (d.Ws & 1))) return;
+        if ((long long)d.row_stride < (long long)d.Ws * (nv12 ? 1 : 3)) return;
         FrameGeom r;
         if (frame_geom(d.Hs, d.Ws, d.decimate, H, W, r) != SY_OK) return;
         r.row_stride = d.row_stride;
         r.dec = sy_uniform(r.dec);                              // the sampling branches on it: scalar, the whole workgroup one way
         g = r; p = d.cur; mirror = d.mirror != 0;
+        fmt = sy_uniform(d.format);
+        fast = sy_uniform(nv12 && nv12_fast_ok(r, (unsigned long long)(uintptr_t)d.cur) ? 1 : 0) != 0;
     }
-    __device__ __forceinline__ float at(int, int, int c, int y, int x) const { return frame_at(p, g, mirror, c, y, x); }
+    __device__ __forceinline__ float at(int, int, int c, int y, int x) const {
+        return frame_at(p, g, mirror, fmt == SY_PIX_RGB ? 2 - c : c, y, x);
+    }
+    __device__ __forceinline__ const unsigned char* image(int, int) const { return p; }
+    __device__ __forceinline__ bool mirrored(int) const { return mirror; }
+    __device__ __forceinline__ void at3(int, int, int y, int x, float o[3]) const { frame_at3_nv12(p, g, mirror, y, x, o); }
 };
 
 struct PlaneSrc {               // fp32 NCHW tensor (Exp.preprocess's input)
@@ -172,6 +320,21 @@ __device__ __forceinline__ float sample(const S& src, int n, int f, int c, int y
            ly.l1 * (lx.l0 * src.at(n, f, c, ly.i1, lx.i0) + lx.l1 * src.at(n, f, c, ly.i1, lx.i1));
 }
 
+// sample() for a source that delivers whole pixels (NV12): the same expressions per channel, every tap converted once
+template <typename S>
+__device__ __forceinline__ void sample3(const S& src, int n, int f, int y, int x, bool resize, float sy, float sx, int H, int W,
+                                        float o[3]) {
+    if (!resize) { src.at3(n, f, y, x, o); return; }
+    const Lerp ly(y, sy, H), lx(x, sx, W);
+    float a[3], b[3], c_[3], d[3];
+    src.at3(n, f, ly.i0, lx.i0, a); src.at3(n, f, ly.i0, lx.i1, b);
+    src.at3(n, f, ly.i1, lx.i0, c_); src.at3(n, f, ly.i1, lx.i1, d);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        o[c] = ly.l0 * (lx.l0 * a[c] + lx.l1 * b[c]) +
+               ly.l1 * (lx.l0 * c_[c] + lx.l1 * d[c]);
+}
+
 // -> fp32 NCHW [B, 3*F, Ho, Wo]; one thread per output element, x fastest (coalesced stores)
 template <typename S>
 __global__ __launch_bounds__(kBlock) void frames_to_nchw_kernel(S src, int B, int F, int H, int W, int Ho, int Wo,
@@ -185,6 +348,86 @@ __global__ __launch_bounds__(kBlock) void frames_to_nchw_kernel(S src, int B, in
         const int ch = (int)((i / ((long long)Wo * Ho)) % (3 * F));
         const int n = (int)(i / ((long long)Wo * Ho * 3 * F));
         out[i] = sample(src, n, ch / 3, ch % 3, y, x, resize, sy, sx, H, W);
+    }
+}
+
+// NV12 -> fp32 NCHW: one thread per output PIXEL, its three channel planes written from one conversion
+__global__ __launch_bounds__(kBlock) void frames_nv12_to_nchw_kernel(FrameSrcNV12 src, int B, int F, int H, int W, int Ho, int Wo,
+                                                                     float* out) {
+    const bool resize = Ho != H || Wo != W;
+    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
+    const long long plane = (long long)Ho * Wo, total = (long long)B * F * plane;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < total; i += (long long)gridDim.x * kBlock) {
+        const int x = (int)(i % Wo);
+        const int y = (int)((i / Wo) % Ho);
+        const int f = (int)((i / plane) % F);
+        const int n = (int)(i / (plane * F));
+        float v[3];
+        sample3(src, n, f, y, x, resize, sy, sx, H, W, v);
+        float* o = out + (((long long)n * F + f) * 3 * Ho + y) * Wo + x;
+        o[0] = v[0]; o[plane] = v[1]; o[2 * plane] = v[2];
+    }
+}
+
+// sixteen elements of one Focus pixel -> dst (two or four 16-byte stores)
+template <typename T>
+__device__ __forceinline__ void focus_store(const typename T::elem (&o)[16], typename T::elem* dst_elems) {
+    typedef typename T::elem elem;
+    uint4* dst = reinterpret_cast<uint4*>(dst_elems);
+    constexpr int NV = (int)(16 * sizeof(elem) / 16);
+    uint4 v[NV];
+    __builtin_memcpy(v, o, sizeof(o));
+#pragma unroll
+    for (int k = 0; k < NV; ++k) dst[k] = v[k];
+}
+
+// focus_pixel for a source that delivers whole pixels (NV12).  FAST (a wave-uniform property of the image, nv12_fast_ok, and no
+// canvas resize): a Focus pixel wholly inside the image comes from nv12_focus_block's wide loads.
+template <typename T, typename S>
+__device__ __forceinline__ void focus_pixel3(const S& src, bool fast, int n, int f, int h2, int w2, bool resize, float sy, float sx,
+                                             int H, int W, typename T::elem* dst_elems) {
+    typedef typename T::elem elem;
+    elem o[16];
+    if (fast && 2 * h2 + 1 < src.g.hs && 2 * w2 + 1 < src.g.ws) {
+        int px[2][2][3];
+        const bool mirror = src.mirrored(n);
+        nv12_focus_block(src.image(n, f), src.g, mirror, h2, w2, px);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                o[q * 3 + c] = T::from_f32((float)(mirror ? px[q & 1][1 - (q >> 1)][c] : px[q & 1][q >> 1][c]));
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float v[3];
+            sample3(src, n, f, 2 * h2 + (q & 1), 2 * w2 + (q >> 1), resize, sy, sx, H, W, v);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[q * 3 + c] = T::from_f32(v[c]);
+        }
+    }
+#pragma unroll
+    for (int c = 12; c < 16; ++c) o[c] = T::from_f32(0.0f);
+    focus_store<T>(o, dst_elems);
+}
+
+// NV12 -> Focus-packed NHWC16, the indexing of frames_to_focus_kernel.  FAST: chosen per launch by the host (nv12_fast_ok over
+// both base pointers and the image stride, no canvas resize)
+template <typename T, bool FAST>
+__global__ __launch_bounds__(kBlock) void frames_nv12_to_focus_kernel(FrameSrcNV12 src, int B, int F, int H, int W, int Ho, int Wo,
+                                                                      typename T::elem* out0, typename T::elem* out1) {
+    const bool resize = Ho != H || Wo != W;
+    const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
+    const int H2 = Ho >> 1, W2 = Wo >> 1;
+    const long long per_frame = (long long)B * H2 * W2;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < per_frame * F; i += (long long)gridDim.x * kBlock) {
+        const int f = (int)(i / per_frame);
+        const long long r = i - f * per_frame;
+        const int w2 = (int)(r % W2);
+        const int h2 = (int)((r / W2) % H2);
+        const int n = (int)(r / ((long long)W2 * H2));
+        focus_pixel3<T>(src, FAST, n, f, h2, w2, resize, sy, sx, H, W, (f == 0 ? out0 : out1) + r * 16);
     }
 }
 
@@ -237,6 +480,15 @@ __global__ __launch_bounds__(kBlock) void rows_to_nchw_kernel(const sy_frame_src
     const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
     const int per_row = 3 * Ho * Wo;
     float* o = out + (long long)n * per_row;
+    if (src.fmt == SY_PIX_NV12) {                               // (scalar) one thread per pixel, three planes from one conversion
+        const int plane = Ho * Wo;
+        for (int i = blockIdx.x * kBlock + threadIdx.x; i < plane; i += gridDim.x * kBlock) {
+            float v[3];
+            sample3(src, n, 0, i / Wo, i % Wo, resize, sy, sx, H, W, v);
+            o[i] = v[0]; o[plane + i] = v[1]; o[2 * plane + i] = v[2];
+        }
+        return;
+    }
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < per_row; i += gridDim.x * kBlock) {
         const int x = i % Wo, y = (i / Wo) % Ho, c = i / (Wo * Ho);
         o[i] = sample(src, n, 0, c, y, x, resize, sy, sx, H, W);
@@ -253,6 +505,12 @@ __global__ __launch_bounds__(kBlock) void rows_to_focus_kernel(const sy_frame_sr
     const int H2 = Ho >> 1, W2 = Wo >> 1;
     const int per_row = H2 * W2;
     typename T::elem* o = out + (long long)n * per_row * 16;
+    if (src.fmt == SY_PIX_NV12) {                               // (scalar: the whole workgroup one way)
+        const bool fast = src.fast && !resize;
+        for (int r = blockIdx.x * kBlock + threadIdx.x; r < per_row; r += gridDim.x * kBlock)
+            focus_pixel3<T>(src, fast, n, 0, r / W2, r % W2, resize, sy, sx, H, W, o + (long long)r * 16);
+        return;
+    }
     for (int r = blockIdx.x * kBlock + threadIdx.x; r < per_row; r += gridDim.x * kBlock)
         focus_pixel<T>(src, n, 0, r / W2, r % W2, resize, sy, sx, H, W, o + (long long)r * 16);
 }
@@ -266,31 +524,83 @@ inline dim3 rows_grid(long long per_row, int B) {
 
 }  // namespace
 
-extern "C" int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, int Hs, int Ws, int64_t image_stride,
-                                 int row_stride, int decimate, const uint8_t* mirror, int H, int W, int Ho, int Wo,
-                                 int layout, void* out_cur, void* out_sup, int dtype, void* stream) {
-    if (cur == nullptr || out_cur == nullptr || B <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
-        return SY_ERR_ARG;
-    if (decimate < -1 || decimate > 2) return SY_ERR_UNSUPPORTED;
-    if (decimate == 2 && ((Hs & 1) || (Ws & 1))) return SY_ERR_UNSUPPORTED;
-    if (row_stride < Ws * 3 || image_stride < (int64_t)row_stride * Hs) return SY_ERR_ARG;
-    FrameSrc src;
-    const int rc = frame_geom(Hs, Ws, decimate, H, W, src.g);
-    if (rc != SY_OK) return rc;
-    const int F = sup != nullptr ? 2 : 1;
-    src.img[0] = cur; src.img[1] = sup; src.image_stride = image_stride; src.g.row_stride = row_stride;
-    src.mirror = mirror;
+namespace {
+
+// S = FrameSrc (BGR: the launches sy_frames_u8_pack always made) or FrameSrcRGB
+template <typename S>
+int frames_pack_launch(const S& src, int B, int F, int H, int W, int Ho, int Wo, int layout, void* out_cur, void* out_sup, int dtype,
+                       void* stream) {
     if (layout == SY_FRAMES_NCHW) {
         const long long work = (long long)B * F * 3 * Ho * Wo;
-        SY_LAUNCH((frames_to_nchw_kernel<FrameSrc>), dim3(grid_for(work)), dim3(kBlock), 0, stream, src, B, F, H, W, Ho, Wo,
+        SY_LAUNCH((frames_to_nchw_kernel<S>), dim3(grid_for(work)), dim3(kBlock), 0, stream, src, B, F, H, W, Ho, Wo,
                   (float*)out_cur);
         return SY_LAUNCH_OK() == 0 ? SY_OK : SY_ERR_LAUNCH;
     }
     if (layout != SY_FRAMES_FOCUS) return SY_ERR_ARG;
     if ((Ho & 1) || (Wo & 1) || (F == 2 && out_sup == nullptr)) return SY_ERR_ARG;
     const long long work = (long long)B * F * (Ho / 2) * (Wo / 2);
-    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((frames_to_focus_kernel<T, FrameSrc>), dim3(grid_for(work)), dim3(kBlock), 0, stream,
+    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((frames_to_focus_kernel<T, S>), dim3(grid_for(work)), dim3(kBlock), 0, stream,
                                        src, B, F, H, W, Ho, Wo, (typename T::elem*)out_cur, (typename T::elem*)out_sup));
+}
+
+int frames_pack_launch_nv12(const FrameSrcNV12& src, int B, int F, int H, int W, int Ho, int Wo, int layout, void* out_cur,
+                            void* out_sup, int dtype, void* stream) {
+    if (layout == SY_FRAMES_NCHW) {
+        const long long work = (long long)B * F * Ho * Wo;
+        SY_LAUNCH(frames_nv12_to_nchw_kernel, dim3(grid_for(work)), dim3(kBlock), 0, stream, src, B, F, H, W, Ho, Wo,
+                  (float*)out_cur);
+        return SY_LAUNCH_OK() == 0 ? SY_OK : SY_ERR_LAUNCH;
+    }
+    if (layout != SY_FRAMES_FOCUS) return SY_ERR_ARG;
+    if ((Ho & 1) || (Wo & 1) || (F == 2 && out_sup == nullptr)) return SY_ERR_ARG;
+    const long long work = (long long)B * F * (Ho / 2) * (Wo / 2);
+    const unsigned long long bits = (unsigned long long)(uintptr_t)src.img[0] | (unsigned long long)(uintptr_t)src.img[1] |
+                                    (unsigned long long)src.image_stride;
+    if (Ho == H && Wo == W && nv12_fast_ok(src.g, bits)) {
+        SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((frames_nv12_to_focus_kernel<T, true>), dim3(grid_for(work)), dim3(kBlock), 0, stream,
+                                           src, B, F, H, W, Ho, Wo, (typename T::elem*)out_cur, (typename T::elem*)out_sup));
+    }
+    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((frames_nv12_to_focus_kernel<T, false>), dim3(grid_for(work)), dim3(kBlock), 0, stream,
+                                       src, B, F, H, W, Ho, Wo, (typename T::elem*)out_cur, (typename T::elem*)out_sup));
+}
+
+}  // namespace
+
+extern "C" int sy_frames_u8_pack_fmt(const uint8_t* cur, const uint8_t* sup, int B, int Hs, int Ws, int64_t image_stride,
+                                     int row_stride, int decimate, const uint8_t* mirror, int H, int W, int Ho, int Wo,
+                                     int layout, void* out_cur, void* out_sup, int dtype, int format, void* stream) {
+    if (cur == nullptr || out_cur == nullptr || B <= 0 || Hs <= 0 || Ws <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0)
+        return SY_ERR_ARG;
+    if (format != SY_PIX_BGR && format != SY_PIX_RGB && format != SY_PIX_NV12) return SY_ERR_ARG;
+    const bool nv12 = format == SY_PIX_NV12;
+    if (decimate < -1 || decimate > 2) return SY_ERR_UNSUPPORTED;
+    if ((decimate == 2 || nv12) && ((Hs & 1) || (Ws & 1))) return SY_ERR_UNSUPPORTED;
+    if (nv12 ? (row_stride < Ws || image_stride < (int64_t)row_stride * Hs * 3 / 2)
+             : (row_stride < Ws * 3 || image_stride < (int64_t)row_stride * Hs)) return SY_ERR_ARG;
+    FrameSrc src;
+    const int rc = frame_geom(Hs, Ws, decimate, H, W, src.g);
+    if (rc != SY_OK) return rc;
+    const int F = sup != nullptr ? 2 : 1;
+    src.img[0] = cur; src.img[1] = sup; src.image_stride = image_stride; src.g.row_stride = row_stride;
+    src.mirror = mirror;
+    if (nv12) {
+        FrameSrcNV12 s;
+        static_cast<FrameSrc&>(s) = src;
+        return frames_pack_launch_nv12(s, B, F, H, W, Ho, Wo, layout, out_cur, out_sup, dtype, stream);
+    }
+    if (format == SY_PIX_RGB) {
+        FrameSrcRGB s;
+        static_cast<FrameSrc&>(s) = src;
+        return frames_pack_launch(s, B, F, H, W, Ho, Wo, layout, out_cur, out_sup, dtype, stream);
+    }
+    return frames_pack_launch(src, B, F, H, W, Ho, Wo, layout, out_cur, out_sup, dtype, stream);
+}
+
+extern "C" int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, int Hs, int Ws, int64_t image_stride,
+                                 int row_stride, int decimate, const uint8_t* mirror, int H, int W, int Ho, int Wo,
+                                 int layout, void* out_cur, void* out_sup, int dtype, void* stream) {
+    return sy_frames_u8_pack_fmt(cur, sup, B, Hs, Ws, image_stride, row_stride, decimate, mirror, H, W, Ho, Wo, layout, out_cur,
+                                 out_sup, dtype, SY_PIX_BGR, stream);
 }
 
 extern "C" int sy_frames_u8_pack_rows(const sy_frame_src* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import PIX_NV12, pixel_format_code
 
 
 class FramePairsU8:
@@ -25,6 +26,10 @@ class FramePairsU8:
     [B, 6, H, W] input tensor (`mode='off_pipe'`) or, with `sup=None`, its [B, 3, H, W] on_pipe frame.
 
     cur, sup : uint8 [B, Hs, Ws, 3] (BGR, as cv2.imread delivers them), same strides
+    pixel_format : "bgr", or "rgb" (the same shape; PIL, torchvision, GStreamer), or "nv12" (hardware video decoders): cur / sup
+               are uint8 [B, Hs*3/2, Ws] — Hs luma rows, then Hs/2 rows of interleaved (U, V), Hs and Ws even; stride(1) may
+               exceed Ws (a decoder's pitch), the innermost stride is 1.  The pack kernel converts per source pixel (BT.601
+               limited range, csrc/input_pipeline.hip): the result is what the BGR path gives for the converted frame
     canvas   : (H, W) letterbox size = exp.input_size / exp.test_size; the frames sit top-left on a 114 canvas
     decimate : 1, or 2 for the exact 2x load-time resize (Argoverse 1200x1920 -> 600x960), or 0 for any other camera
                size: `preproc`'s r = min(H / h, W / w) bilinear letterbox resize (OpenCV fixed-point arithmetic), or -1
@@ -35,9 +40,18 @@ class FramePairsU8:
     Quacks like the tensor it replaces where the model facades look at their input (`shape`, `size()`, `dtype`,
     `device`, `is_cuda`, `float()`, `contiguous()`)."""
 
-    def __init__(self, cur, sup, canvas, decimate=1, mirror=None, out_size=None):
-        assert cur.dtype == torch.uint8 and cur.dim() == 4 and cur.shape[-1] == 3
-        self.cur, self.sup = cur.contiguous(), (None if sup is None else sup.contiguous())
+    def __init__(self, cur, sup, canvas, decimate=1, mirror=None, out_size=None, pixel_format="bgr"):
+        self.pixel_format = pixel_format
+        if pixel_format_code(pixel_format) == PIX_NV12:
+            assert cur.dtype == torch.uint8 and cur.dim() == 3 and cur.stride(2) == 1
+            if cur.shape[1] % 3 or cur.shape[2] % 2:               # (rows = Hs * 3 / 2 with Hs even <=> rows % 3 == 0)
+                raise ValueError("FramePairsU8: NV12 images are uint8 [B, Hs*3/2, Ws] with Hs and Ws even, got %s"
+                                 % (tuple(cur.shape),))
+            assert sup is None or (sup.shape == cur.shape and sup.stride() == cur.stride())
+            self.cur, self.sup = cur, sup                        # (a pitch above Ws is part of the format: no repacking)
+        else:
+            assert cur.dtype == torch.uint8 and cur.dim() == 4 and cur.shape[-1] == 3
+            self.cur, self.sup = cur.contiguous(), (None if sup is None else sup.contiguous())
         self.canvas = (int(canvas[0]), int(canvas[1]))
         self.decimate = int(decimate)
         self.mirror = None if mirror is None else mirror.to(device=cur.device, dtype=torch.uint8).contiguous()
@@ -69,24 +83,26 @@ class FramePairsU8:
 
     def resized(self, tsize):
         """Same frames, run at `tsize` (the bilinear resize happens inside the pack kernel)."""
-        return FramePairsU8(self.cur, self.sup, self.canvas, self.decimate, self.mirror, tsize)
+        return FramePairsU8(self.cur, self.sup, self.canvas, self.decimate, self.mirror, tsize, self.pixel_format)
 
     def paired_with_self(self):
         """3-channel input on the off_pipe path: the reference duplicates it (dfp_pafpn.py:236-238)."""
         return self if self.sup is not None else FramePairsU8(self.cur, self.cur, self.canvas, self.decimate,
-                                                             self.mirror, self.out_size)
+                                                             self.mirror, self.out_size, self.pixel_format)
 
     # ---- materialisation ---------------------------------------------------------------------------------
     def to_nchw(self):
         """The reference's own input tensor: fp32 [B, 3|6, Ho, Wo] (drop-in for any consumer of `inps`)."""
         out = torch.empty(tuple(self.shape), dtype=torch.float32, device=self.device)
-        ops.frames_u8_pack(self.cur, self.sup, self.canvas, self.out_size, out, None, self.decimate, self.mirror)
+        ops.frames_u8_pack(self.cur, self.sup, self.canvas, self.out_size, out, None, self.decimate, self.mirror,
+                           self.pixel_format)
         return out
 
     def pack_focus(self, cur_view, sup_view=None):
         """Write the stem operand(s) (Focus-packed NHWC16 Views of the plan) straight from the uint8 frames."""
         assert (sup_view is None) == (self.sup is None)
-        ops.frames_u8_pack(self.cur, self.sup, self.canvas, self.out_size, cur_view, sup_view, self.decimate, self.mirror)
+        ops.frames_u8_pack(self.cur, self.sup, self.canvas, self.out_size, cur_view, sup_view, self.decimate, self.mirror,
+                           self.pixel_format)
 
 
 def row_geometry(frame_hw, canvas, decimate=None):
@@ -120,7 +136,7 @@ def row_geometry(frame_hw, canvas, decimate=None):
 
 # sy_frame_src (include/streamyolo_hip.h), one per batch row
 _ROW_DTYPE = np.dtype([("cur", "<u8"), ("Hs", "<i4"), ("Ws", "<i4"), ("row_stride", "<i4"), ("decimate", "<i4"),
-                       ("mirror", "<i4"), ("reserved", "<i4")])
+                       ("mirror", "<i4"), ("format", "<i4")])
 assert _ROW_DTYPE.itemsize == 32
 
 
@@ -130,8 +146,9 @@ class FrameRowsU8(FramePairsU8):
     (sy_frames_u8_pack_rows) — which camera sits in which row is data, so one recorded launch serves every mix.
 
     Owns a byte staging arena [batch, Hmax * Wmax * 3] on the device (set_row copies a frame contiguously into its row's
-    bytes, row_stride = 3 Ws) and the table with a per-row box divisor behind it: ONE device buffer with pinned host mirrors
-    of the same layout, upload() is a single non-blocking copy.  A row without a frame is the plain 114 canvas.
+    bytes, row_stride = 3 Ws; an NV12 frame takes half of that, row_stride = Ws — the pixel format is per-row data too) and
+    the table with a per-row box divisor behind it: ONE device buffer with pinned host mirrors of the same layout, upload()
+    is a single non-blocking copy.  A row without a frame is the plain 114 canvas.
 
         rows = FrameRowsU8(batch, (Hmax, Wmax), canvas, device)
         rows.set_row(0, frame_a); rows.set_row(1, None); rows.upload()
@@ -160,13 +177,16 @@ class FrameRowsU8(FramePairsU8):
         # what the plans look at (FramePairsU8's surface): the arena stands for the frames, the table is part of the tape key
         self.cur, self.sup, self.mirror = self.arena, None, None
         self.decimate = ("rows", self.table.data_ptr())
+        self.pixel_format = "rows"                                   # per row, in the table
         self.upload()
 
-    def set_row(self, b, frame, mirror=False, decimate=None, divisor=None):
+    def set_row(self, b, frame, mirror=False, decimate=None, divisor=None, pixel_format="bgr"):
         """Row b of the next upload() (host table; the pixels go to the arena on the current stream): `frame` uint8 [Hs, Ws, 3]
-        (array or tensor, host or device) or None = no frame.  decimate as FramePairsU8 (None: by size, see row_geometry);
-        divisor: what the row's boxes are divided by (default: the letterbox ratio r).  ValueError — before anything is
-        written — for a frame this object cannot hold or the kernel would refuse."""
+        (array or tensor, host or device; pixel_format "bgr" or "rgb") or uint8 [Hs*3/2, Ws] ("nv12", Hs and Ws even) or None =
+        no frame.  decimate as FramePairsU8 (None: by size, see row_geometry); divisor: what the row's boxes are divided by
+        (default: the letterbox ratio r).  ValueError — before anything is written — for a frame this object cannot hold or
+        the kernel would refuse."""
+        fmt = pixel_format_code(pixel_format)
         if not 0 <= b < self.batch:
             raise ValueError("FrameRowsU8: row %r of %d" % (b, self.batch))
         if frame is None:
@@ -174,9 +194,15 @@ class FrameRowsU8(FramePairsU8):
             self._div[b] = 1.0
             return
         f = torch.as_tensor(frame)
-        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
+        if fmt == PIX_NV12:
+            if f.dtype != torch.uint8 or f.dim() != 2 or f.shape[0] % 3 or f.shape[1] % 2:
+                raise ValueError("FrameRowsU8: NV12 frames must be uint8 [Hs*3/2, Ws] with Hs and Ws even, got %s %s"
+                                 % (f.dtype, tuple(f.shape)))
+            hs, ws = int(f.shape[0]) // 3 * 2, int(f.shape[1])
+        elif f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
             raise ValueError("FrameRowsU8: frames must be uint8 [Hs, Ws, 3], got %s %s" % (f.dtype, tuple(f.shape)))
-        hs, ws = int(f.shape[0]), int(f.shape[1])
+        else:
+            hs, ws = int(f.shape[0]), int(f.shape[1])
         if hs > self.max_frame_hw[0] or ws > self.max_frame_hw[1]:
             raise ValueError("FrameRowsU8: a %dx%d frame is above max_frame_hw %dx%d" % ((hs, ws) + self.max_frame_hw))
         dec, r = row_geometry((hs, ws), self.canvas, decimate)
@@ -184,8 +210,12 @@ class FrameRowsU8(FramePairsU8):
             if r is None:
                 raise ValueError("FrameRowsU8: decimate -1 has no single ratio, pass divisor")
             divisor = r
-        self.arena[b, :hs * ws * 3].view(hs, ws, 3).copy_(f, non_blocking=True)
-        self._rows[b] = (self.arena.data_ptr() + b * self.arena.stride(0), hs, ws, ws * 3, dec, 1 if mirror else 0, 0)
+        if fmt == PIX_NV12:
+            self.arena[b, :hs * ws * 3 // 2].view(hs * 3 // 2, ws).copy_(f, non_blocking=True)
+        else:
+            self.arena[b, :hs * ws * 3].view(hs, ws, 3).copy_(f, non_blocking=True)
+        self._rows[b] = (self.arena.data_ptr() + b * self.arena.stride(0), hs, ws, ws if fmt == PIX_NV12 else ws * 3, dec,
+                         1 if mirror else 0, fmt)
         self._div[b] = divisor
 
     def upload(self):
@@ -253,11 +283,14 @@ class DevicePrefetcher:
     H2D copies run on a side stream while the current step computes; `next()` makes the current stream wait for
     them and pins their memory to it (`record_stream`), exactly as the reference hands its fp32 batch over.
 
-    `loader` yields ((cur_u8 [B,Hs,Ws,3], sup_u8, mirror [B] or None), (labels, support_labels), ...)."""
+    `loader` yields ((cur_u8 [B,Hs,Ws,3], sup_u8, mirror [B] or None), (labels, support_labels), ...); with
+    pixel_format "nv12" the frames are [B,Hs*3/2,Ws] (decoder output), see FramePairsU8."""
 
-    def __init__(self, loader, canvas, decimate=1, device="cuda"):
+    def __init__(self, loader, canvas, decimate=1, device="cuda", pixel_format="bgr"):
         self.loader = iter(loader)
         self.canvas, self.decimate, self.device = canvas, decimate, torch.device(device)
+        pixel_format_code(pixel_format)                              # (ValueError for an unknown one, before the first batch)
+        self.pixel_format = pixel_format
         self.stream = torch.cuda.Stream(self.device)
         self.preload()
 
@@ -272,7 +305,7 @@ class DevicePrefetcher:
             cur = cur.to(self.device, non_blocking=True)
             sup = None if sup is None else sup.to(self.device, non_blocking=True)
             mirror = None if mirror is None else torch.as_tensor(mirror, dtype=torch.uint8).to(self.device, non_blocking=True)
-            self.next_input = FramePairsU8(cur, sup, self.canvas, self.decimate, mirror)
+            self.next_input = FramePairsU8(cur, sup, self.canvas, self.decimate, mirror, pixel_format=self.pixel_format)
             self.next_target = (target[0].to(self.device, non_blocking=True), target[1].to(self.device, non_blocking=True))
 
     def next(self):

@@ -628,7 +628,9 @@ class InferencePlan:
     # side of a frame drops from 4.6 to 3.4 ms and stays below the 3.7 ms of kernels, so a caller that cannot hold a
     # hipGraph (StreamingDetector: first-frame variant, per-sequence reset) still runs at the graph's latency.
     def _tape_signature(self, x, check_params=True):
-        src = (x.cur.data_ptr(), None if x.mirror is None else x.mirror.data_ptr(), x.canvas, x.out_size, x.decimate) \
+        # (pixel_format: a scalar argument of the recorded pack launch; strides: an NV12 pitch is one too)
+        src = (x.cur.data_ptr(), None if x.mirror is None else x.mirror.data_ptr(), x.canvas, x.out_size, x.decimate,
+               x.pixel_format, tuple(x.cur.shape), tuple(x.cur.stride())) \
             if isinstance(x, FramePairsU8) else (x.data_ptr(), x.dtype, tuple(x.shape))
         # check_params=False: the caller guarantees frozen weights (streaming inference) and saves ~0.1 ms of host time
         return src, ((ops.weights_epoch(),) + tuple((p.data_ptr(), p._version) for p in self._tape_params())

@@ -217,12 +217,18 @@ def focus_pack(frames, c0, out):
 FRAMES_NCHW, FRAMES_FOCUS = 0, 1
 
 
-def frames_u8_pack(cur, sup, canvas, out_size, out_cur, out_sup=None, decimate=1, mirror=None):
-    """cur / sup: uint8 [B, Hs, Ws, 3] device tensors (sup None = single frame).  canvas = (H, W) letterbox size
-    (exp.input_size / test_size), out_size = (Ho, Wo).  out_cur: fp32 tensor [B, 3|6, Ho, Wo] (NCHW layout) or a
-    Focus-packed View [B, Ho/2, Wo/2, 16]; then out_sup is the support frame's View."""
-    assert cur.dtype == torch.uint8 and cur.dim() == 4 and cur.shape[3] == 3 and cur.stride(3) == 1 and cur.stride(2) == 3
-    B, Hs, Ws, _ = cur.shape
+def frames_u8_pack(cur, sup, canvas, out_size, out_cur, out_sup=None, decimate=1, mirror=None, pixel_format="bgr"):
+    """cur / sup: uint8 [B, Hs, Ws, 3] device tensors (sup None = single frame) in BGR or — pixel_format "rgb" — RGB order, or
+    — "nv12" — uint8 [B, Hs*3/2, Ws] NV12 images (luma rows, then the interleaved chroma rows; stride(1) may exceed Ws).
+    canvas = (H, W) letterbox size (exp.input_size / test_size), out_size = (Ho, Wo).  out_cur: fp32 tensor
+    [B, 3|6, Ho, Wo] (NCHW layout) or a Focus-packed View [B, Ho/2, Wo/2, 16]; then out_sup is the support frame's View."""
+    fmt = _lib.pixel_format_code(pixel_format)
+    if fmt == _lib.PIX_NV12:
+        assert cur.dtype == torch.uint8 and cur.dim() == 3 and cur.stride(2) == 1 and cur.shape[1] % 3 == 0
+        B, Hs, Ws = cur.shape[0], cur.shape[1] // 3 * 2, cur.shape[2]
+    else:
+        assert cur.dtype == torch.uint8 and cur.dim() == 4 and cur.shape[3] == 3 and cur.stride(3) == 1 and cur.stride(2) == 3
+        B, Hs, Ws, _ = cur.shape
     if sup is not None:
         assert sup.dtype == torch.uint8 and sup.shape == cur.shape and sup.stride() == cur.stride()
     if mirror is not None:
@@ -239,9 +245,16 @@ def frames_u8_pack(cur, sup, canvas, out_size, out_cur, out_sup=None, decimate=1
         assert out_cur.dtype == torch.float32 and out_cur.is_contiguous()
         assert tuple(out_cur.shape) == (B, 3 if sup is None else 6, Ho, Wo)
         po, ps = out_cur.data_ptr(), None
-    check(_lib.lib().sy_frames_u8_pack(cur.data_ptr(), _p(sup), B, Hs, Ws, cur.stride(0), cur.stride(1), int(decimate),
-                                       _p(mirror), H, W, Ho, Wo, layout, po, ps, dt, stream_of(cur)),
-          "sy_frames_u8_pack")
+    if fmt == _lib.PIX_BGR:                                       # the call it always was (launch tapes record the name)
+        check(_lib.lib().sy_frames_u8_pack(cur.data_ptr(), _p(sup), B, Hs, Ws, cur.stride(0), cur.stride(1), int(decimate),
+                                           _p(mirror), H, W, Ho, Wo, layout, po, ps, dt, stream_of(cur)),
+              "sy_frames_u8_pack")
+        return
+    # (a batch of one: torch does not define the stride of a size-1 dimension — numpy's a[None] arrives with 0)
+    image_stride = cur.stride(0) if B > 1 else max(cur.stride(0), cur.shape[1] * cur.stride(1))
+    check(_lib.lib().sy_frames_u8_pack_fmt(cur.data_ptr(), _p(sup), B, Hs, Ws, image_stride, cur.stride(1), int(decimate),
+                                           _p(mirror), H, W, Ho, Wo, layout, po, ps, dt, fmt, stream_of(cur)),
+          "sy_frames_u8_pack_fmt")
 
 
 def frames_u8_pack_rows(table, B, canvas, out_size, out):

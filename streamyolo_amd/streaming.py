@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import PIX_NV12, pixel_format_code
 from .data import FramePairsU8, FrameRowsU8, row_geometry
 from .postprocess import postprocess_device
 
@@ -31,6 +32,17 @@ def inference(outputs, num_classes=8, conf_thre=0.01, nms_thresh=0.65, in_scale=
     pred = outputs if outputs.dim() == 3 else outputs.unsqueeze(0)
     det, _, cnt = postprocess_device(pred, num_classes, conf_thre, nms_thresh)
     return _parse(det, cnt, in_scale)
+
+
+def frame_shape(frame_hw, pixel_format="bgr"):
+    """Shape of one uint8 camera frame of size frame_hw = (h, w): (h, w, 3) for "bgr" / "rgb", (h * 3 / 2, w) for "nv12" (luma
+    rows, then the interleaved chroma rows).  ValueError for an unknown format or an odd NV12 size."""
+    h, w = int(frame_hw[0]), int(frame_hw[1])
+    if pixel_format_code(pixel_format) != PIX_NV12:
+        return (h, w, 3)
+    if h % 2 or w % 2:
+        raise ValueError("NV12 frames have even sizes, got %dx%d" % (h, w))
+    return (h * 3 // 2, w)
 
 
 def _parse(det, cnt, in_scale):
@@ -49,10 +61,13 @@ class StreamingDetector:
     (h_img, w_img) = (int(H * in_scale), int(W * in_scale)) with cv2.resize(img, (w_img, h_img)) (:176-178: truncation, each
     axis stretched on its own): with in_scale = 0.5 on even frames that is the exact 2x decimation, with any other in_scale
     OpenCV's fixed-point bilinear resize — both done on the device together with the Focus packing (sy_frames_u8_pack,
-    csrc/input_pipeline.hip)."""
+    csrc/input_pipeline.hip).  pixel_format "rgb" / "nv12": the frames arrive in that format (frame_shape()) and the same
+    launch converts them, as cv2.cvtColor in front of the loop would."""
 
     def __init__(self, model, frame_hw, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65, dtype="fp16",
-                 device="cuda"):
+                 device="cuda", pixel_format="bgr"):
+        self.pixel_format = pixel_format
+        self._frame_shape = frame_shape(frame_hw, pixel_format)      # (ValueError before anything is built)
         self.model = model.to(device).eval().set_compute_dtype(dtype)
         self.device = torch.device(device)
         self.in_scale = in_scale
@@ -69,8 +84,8 @@ class StreamingDetector:
         else:
             self.decimate = -1                                    # per-axis fixed-point bilinear stretch to the canvas
         self.num_classes, self.conf_thre, self.nms_thresh = num_classes, conf_thre, nms_thresh
-        self._slot = torch.empty((1,) + self.frame_hw + (3,), dtype=torch.uint8, device=self.device)
-        self._in = FramePairsU8(self._slot, None, self.canvas, self.decimate)
+        self._slot = torch.empty((1,) + self._frame_shape, dtype=torch.uint8, device=self.device)
+        self._in = FramePairsU8(self._slot, None, self.canvas, self.decimate, pixel_format=pixel_format)
         # 16-bit speed modes: the deep small-map layers may run as split-K (different fp32 summation order than the facade's
         # exact path — a plan object of its own); the fp32 parity mode keeps the single-pass kernels
         split_k = str(dtype) not in ("fp32", "torch.float32") and os.environ.get("STREAMYOLO_STREAM_SPLITK", "1") != "0"
@@ -92,10 +107,10 @@ class StreamingDetector:
         self._first = True
 
     def __call__(self, frame):
-        """One camera frame (uint8 [H, W, 3] numpy array or tensor) -> (bboxes, scores, labels, None), host arrays.
-        Ends with the device synchronised (the D2H copy of the detections), as the reference's loop does (:183)."""
+        """One camera frame (uint8 [H, W, 3] numpy array or tensor; [H*3/2, W] for "nv12") -> (bboxes, scores, labels, None),
+        host arrays.  Ends with the device synchronised (the D2H copy of the detections), as the reference's loop does (:183)."""
         f = torch.as_tensor(frame)
-        assert f.dtype == torch.uint8 and tuple(f.shape) == self.frame_hw + (3,)
+        assert f.dtype == torch.uint8 and tuple(f.shape) == self._frame_shape
         self._slot[0].copy_(f, non_blocking=True)
         with torch.no_grad():
             if self._first:                                   # node 'star': extra fan-in copies, through the wrappers
@@ -129,6 +144,10 @@ class MultiStreamDetector:
     canvas) and its boxes are divided by that r, as the evaluators do; a stream opened without one is a `frame_hw` camera
     treated exactly as in the uniform mode.
 
+    pixel_format ("bgr", "rgb", "nv12") is the format the cameras deliver (frame_shape()); the pack launch converts.  In mixed
+    mode it is the default of open(), which may name another per stream: the format sits in the row table beside the size, so
+    cameras of different formats share ticks and the one tape too.
+
         det = MultiStreamDetector(model, (1200, 1920), max_streams=16, batch=8, max_frame_hw=(2048, 2048)); det.warm_up()
         ring, side = det.open(), det.open(frame_hw=(1550, 2048))
         (boxes_r, ...), (boxes_s, ...) = det([ring_frame, side_frame], [ring, side])
@@ -136,7 +155,9 @@ class MultiStreamDetector:
     Which frames go into a tick is the caller's scheduling policy."""
 
     def __init__(self, model, frame_hw, max_streams=16, batch=8, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65,
-                 dtype="fp16", device="cuda", max_frame_hw=None):
+                 dtype="fp16", device="cuda", max_frame_hw=None, pixel_format="bgr"):
+        self.pixel_format = pixel_format
+        self._frame_shape = frame_shape(frame_hw, pixel_format)      # (ValueError before anything is built)
         if int(batch) < 1 or int(max_streams) < 1:
             raise ValueError("MultiStreamDetector: batch and max_streams must be positive")
         if max_frame_hw is not None:
@@ -161,13 +182,14 @@ class MultiStreamDetector:
         self.num_classes, self.conf_thre, self.nms_thresh = num_classes, conf_thre, nms_thresh
         if self.max_frame_hw is None:
             # detector-owned staging: row b of a tick's frames (rows without a frame keep stale pixels; their outputs are ignored)
-            self._stage = torch.zeros((self.batch,) + self.frame_hw + (3,), dtype=torch.uint8, device=self.device)
-            self._in = FramePairsU8(self._stage, None, self.canvas, self.decimate)
+            self._stage = torch.zeros((self.batch,) + self._frame_shape, dtype=torch.uint8, device=self.device)
+            self._in = FramePairsU8(self._stage, None, self.canvas, self.decimate, pixel_format=pixel_format)
         else:
             # mixed mode: a byte arena per row and the per-row descriptor table (rows without a frame are the plain canvas)
             self._stage = None
             self._in = FrameRowsU8(self.batch, self.max_frame_hw, self.canvas, self.device)
         self._geom = {}                                          # mixed mode: open stream id -> (frame hw, decimate, box divisor)
+        self._fmt = {}                                           # open stream id -> (pixel format, shape of its frames)
         split_k = str(dtype) not in ("fp32", "torch.float32") and os.environ.get("STREAMYOLO_STREAM_SPLITK", "1") != "0"
         self.plan = model._plans.inference(model.backbone, model.head, "on_pipe", self._in, owner=model, split_k=split_k)
         from .engine import StreamSlots
@@ -180,10 +202,17 @@ class MultiStreamDetector:
         self._next_id = 0                                        # ids are never reused: a closed id stays invalid
 
     # ---- stream bookkeeping (host side only) --------------------------------------------------------------------
-    def open(self, frame_hw=None):
+    def open(self, frame_hw=None, pixel_format=None):
         """A new stream: its id.  Its first frame fuses with itself (`buffer = None`, streamyolo_det.py:150).  Mixed mode:
-        frame_hw = (h, w) is this stream's camera size for its lifetime (None: the detector's frame_hw and in_scale)."""
+        frame_hw = (h, w) is this stream's camera size for its lifetime (None: the detector's frame_hw and in_scale) and
+        pixel_format its format (None: the detector's).  ValueError — nothing is taken — for what the detector cannot serve."""
         geom = (self.frame_hw, self.decimate, self.in_scale)
+        if pixel_format is None:
+            pixel_format = self.pixel_format
+        pixel_format_code(pixel_format)
+        if self.max_frame_hw is None and pixel_format != self.pixel_format:
+            raise ValueError("MultiStreamDetector: a uniform detector serves %r frames only (open(pixel_format=%r)); build it "
+                             "with max_frame_hw for per-stream formats" % (self.pixel_format, pixel_format))
         if frame_hw is not None:
             if self.max_frame_hw is None:
                 raise ValueError("MultiStreamDetector: open(frame_hw=...) needs a detector built with max_frame_hw")
@@ -192,6 +221,7 @@ class MultiStreamDetector:
                 raise ValueError("MultiStreamDetector: a %dx%d camera is above max_frame_hw %dx%d" % (hw + self.max_frame_hw))
             decimate, r = row_geometry(hw, self.canvas)          # (ValueError: nothing of the frame is left on the canvas)
             geom = (hw, decimate, r)
+        shape = frame_shape(geom[0], pixel_format)               # (ValueError: an odd NV12 size)
         if not self._free:
             raise RuntimeError("MultiStreamDetector: all %d streams are open" % self.max_streams)
         sid = self._next_id
@@ -199,6 +229,7 @@ class MultiStreamDetector:
         self._slot_of[sid] = self._free.pop(0)
         self._first[sid] = True
         self._geom[sid] = geom
+        self._fmt[sid] = (pixel_format, shape)
         return sid
 
     def _known(self, sid):
@@ -217,6 +248,7 @@ class MultiStreamDetector:
         self._free.sort()
         del self._first[sid]
         del self._geom[sid]
+        del self._fmt[sid]
 
     def warm_up(self, n=10):
         """streamyolo_det.py:113-120 on a dummy batch (no row carries a frame: no stream's state is written); builds, tunes and
@@ -250,10 +282,10 @@ class MultiStreamDetector:
         fs = []
         for f, sid in zip(frames, sids):
             f = torch.as_tensor(f)
-            hw = self._geom[sid][0]                              # its stream's camera size (uniform mode: frame_hw)
-            if f.dtype != torch.uint8 or tuple(f.shape) != hw + (3,):
-                raise ValueError("MultiStreamDetector: frames of stream %r must be uint8 [%d, %d, 3], got %s %s"
-                                 % ((sid,) + hw + (f.dtype, tuple(f.shape))))
+            fmt, shape = self._fmt[sid]                          # its stream's format and camera size (uniform mode: frame_hw)
+            if f.dtype != torch.uint8 or tuple(f.shape) != shape:
+                raise ValueError("MultiStreamDetector: frames of stream %r (%s) must be uint8 %s, got %s %s"
+                                 % (sid, fmt, list(shape), f.dtype, tuple(f.shape)))
             fs.append(f)
         return fs
 
@@ -266,7 +298,7 @@ class MultiStreamDetector:
             for b in range(self.batch):
                 if b < n:
                     _, decimate, div = self._geom[sids[b]]
-                    self._in.set_row(b, frames[b], decimate=decimate, divisor=div)
+                    self._in.set_row(b, frames[b], decimate=decimate, divisor=div, pixel_format=self._fmt[sids[b]][0])
                 else:
                     self._in.set_row(b, None)
             self._in.upload()

@@ -88,6 +88,25 @@ def synth_frames(batch, height, width, seed=2, channels=6):
     return torch.rand((batch, channels, height, width), generator=g) * 255.0
 
 
+def bgr_to_nv12(frames):
+    """uint8 [..., Hs, Ws, 3] BGR frames (Hs, Ws even) -> uint8 [..., Hs*3/2, Ws] NV12 on the same device: BT.601 limited range
+    forward (Y = 16 + (65.481 R + 128.553 G + 24.966 B) / 255, ...), rounded, chroma averaged over each 2x2 block.  For tools
+    that want realistic pictures in a decoder's format; NOT an exact inverse of the pack kernel's NV12 -> BGR conversion."""
+    f = torch.as_tensor(frames)
+    hs, ws = f.shape[-3], f.shape[-2]
+    assert f.dtype == torch.uint8 and f.shape[-1] == 3 and hs % 2 == 0 and ws % 2 == 0
+    b, g, r = (f[..., c].float() for c in range(3))
+    y = 16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0
+    u = 128.0 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255.0
+    v = 128.0 + (112.0 * r - 93.786 * g - 18.214 * b) / 255.0
+    lead = f.shape[:-3]
+
+    def sub(c):                                                  # mean of each 2x2 block
+        return c.reshape(lead + (hs // 2, 2, ws // 2, 2)).mean(dim=(-3, -1))
+    uv = torch.stack([sub(u), sub(v)], dim=-1).reshape(lead + (hs // 2, ws))
+    return torch.cat([y, uv], dim=-2).round().clamp(0, 255).to(torch.uint8)
+
+
 def synth_labels(batch, height, width, num_classes=8, num_gt=16, max_labels=120, seed=3):
     """(labels_t+1, labels_t): two [B,120,5] tensors of (cls, cx, cy, w, h) px; zero padded (cfg :80)."""
     g = torch.Generator(device="cpu")

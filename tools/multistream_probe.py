@@ -16,6 +16,13 @@ yardstick; the best round counts.  Prints one JSON line (and writes it to --out)
 (2x decimation), the network input size (copy) and 3/4 x 5/6 of the frame (`preproc`'s letterbox, r = 0.6 for 1200x1920) — all
 packed by the ONE sy_frames_u8_pack_rows launch of the tape.  Every row of the result also carries the uniform detector's tick
 at the same batch, measured in the same process, alternating (`uniform_ms_per_tick`, `mixed_over_uniform`).
+
+--pixel-format nv12 (or rgb): the detector is built for cameras that deliver that format (the same pictures converted on the
+host before the timed region; NV12 frames are half the bytes) and the pack launch converts.  Every row also carries the BGR
+detector's tick at the same batch, measured in the same process, alternating: `bgr_ms_per_tick`, `nv12_over_bgr` (best round
+over best round) and the per-round times of both (`ms_rounds`, `bgr_ms_rounds`: the spread the ratio has to be read against).
+
+    python tools/multistream_probe.py --pixel-format nv12 --batches 1,8 --out profiles/r09/multistream_probe_nv12.json
 """
 import argparse
 import json
@@ -42,6 +49,8 @@ def main():
     ap.add_argument("--trace", type=int, default=0, help="batch: warm up, run 20 ticks of that batch and exit (profiler runs)")
     ap.add_argument("--baseline-only", type=int, default=0, help="1: only the single-camera yardstick (also runs on older trees)")
     ap.add_argument("--mixed", type=int, default=0, help="1: mixed-mode detector, row cameras cycling through three sizes")
+    ap.add_argument("--pixel-format", default="bgr", choices=["bgr", "rgb", "nv12"],
+                    help="the format the cameras deliver; not bgr: timed beside the BGR tick of the same batch")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -50,7 +59,7 @@ def main():
     from oracle import streamyolo_oracle as O
     from streamyolo_amd import _lib
     from streamyolo_amd.streaming import StreamingDetector
-    from streamyolo_amd.utils.synth import synth_state_dict, synth_frames
+    from streamyolo_amd.utils.synth import synth_state_dict, synth_frames, bgr_to_nv12
     _lib.use_library(_lib.DEFAULT_PATH)
     dev = torch.device("cuda:0")
     hw = (args.height, args.width)
@@ -118,6 +127,14 @@ def main():
                 f.write(line + "\n")
         return line
 
+    fmt = args.pixel_format
+    if fmt != "bgr":
+        if args.mixed:
+            ap.error("--pixel-format and --mixed are separate measurements")
+        res["pixel_format"] = fmt
+        fmt_frames = [bgr_to_nv12(f) if fmt == "nv12" else f.flip(-1).contiguous() for f in frames]
+    alt = bool(args.mixed) or fmt != "bgr"                       # a second detector of the batch is timed beside the uniform BGR one
+
     if args.baseline_only:
         single_tick(1)
         for n in sorted(set(batches + [int(v) for v in args.active.split(",") if v])):
@@ -140,6 +157,12 @@ def main():
             sids = [det.open(frame_hw=sizes[i % 3]) for i in range(B)]
             tick_frames = mixed_frames
             det.detect_device(tick_frames[:B], sids)
+        elif fmt != "bgr":
+            det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev, pixel_format=fmt)
+            det.warm_up(args.warmup)
+            sids = [det.open() for _ in range(B)]
+            tick_frames = fmt_frames
+            det.detect_device(tick_frames[:B], sids)
         for n in ([B] if (B != 8 or args.trace) else sorted(set([int(v) for v in args.active.split(",") if v] + [B]))):
             def multi_tick():
                 det.detect_device(tick_frames[:n], sids[:n])
@@ -152,13 +175,16 @@ def main():
                 return
             multi_tick()
             best_m, best_s, host_m, best_u = float("inf"), float("inf"), float("inf"), float("inf")
+            m_rounds, u_rounds = [], []
             for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
-                if args.mixed:
+                if alt:
                     multi_tick()                                 # (two detectors of one batch share the plan: the untimed tick
                 m, h = timed(multi_tick, args.ticks)             #  after a switch re-records its tape)
-                if args.mixed:
+                m_rounds.append(m)
+                if alt:
                     uniform_tick()
-                    best_u = min(best_u, timed(uniform_tick, args.ticks)[0])
+                    u_rounds.append(timed(uniform_tick, args.ticks)[0])
+                    best_u = min(best_u, u_rounds[-1])
                 s, _ = timed(lambda: single_tick(n), args.ticks)
                 best_m, best_s, host_m = min(best_m, m), min(best_s, s), min(host_m, h)
             res["rows"].append({"batch": B, "active": n, "ms_per_tick": best_m, "frames_per_s": 1e3 * n / best_m,
@@ -166,6 +192,10 @@ def main():
                                 "single_frames_per_s": 1e3 * n / best_s, "tick_over_n_single_frames": best_m / best_s})
             if args.mixed:
                 res["rows"][-1].update({"mixed": True, "uniform_ms_per_tick": best_u, "mixed_over_uniform": best_m / best_u})
+            elif fmt != "bgr":
+                res["rows"][-1].update({"pixel_format": fmt, "bgr_ms_per_tick": best_u, "%s_over_bgr" % fmt: best_m / best_u,
+                                        "ms_rounds": m_rounds, "bgr_ms_rounds": u_rounds,
+                                        "bgr_spread_over_rounds": (max(u_rounds) - min(u_rounds)) / min(u_rounds)})
             emit()
         del det, uni                                             # (their plans and pools go back to the allocator)
     print(emit())
