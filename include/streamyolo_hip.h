@@ -186,7 +186,8 @@ SY_API int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, int 
  *   SY_PIX_NV12  what hardware video decoders deliver: cur / sup are [B] images of Hs * 3 / 2 rows of ONE pitch
  *                (row_stride >= Ws bytes): Hs rows of luma, then — starting at row Hs — Hs / 2 rows of interleaved chroma
  *                (U, V): the [Hs * 3 / 2, Ws] array cv2.cvtColor(.., COLOR_YUV2BGR_NV12) takes, with an optional pitch.
- *                Surfaces whose chroma plane starts elsewhere (a padded luma height, a detached plane) are NOT supported.
+ *                A surface whose chroma plane starts elsewhere (a padded luma height, a detached plane, a pitch of its
+ *                own) goes through sy_frames_u8_pack_surfaces below, which reads it in place.
  *                Hs and Ws even (else SY_ERR_UNSUPPORTED); image_stride >= row_stride * Hs * 3 / 2 (else SY_ERR_ARG).
  *                Chroma of pixel (y, x) = the pair at chroma row y >> 1, byte 2 * (x >> 1): nearest, no interpolation.
  *                BT.601 limited range in int32 fixed point, as OpenCV publishes it for COLOR_YUV2BGR_NV12 (restated from
@@ -220,6 +221,44 @@ typedef struct sy_frame_src {      /* 32 bytes */
 } sy_frame_src;
 SY_API int sy_frames_u8_pack_rows(const sy_frame_src* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,
                                   int dtype, void* stream);
+
+/* sy_frames_u8_pack_rows for hardware decoder surfaces, read where they lie: every row names BOTH planes, each with a pitch of
+ * its own, so a padded luma height (a 1080-row stream decodes into 1088 luma rows), a chroma plane in its own allocation and a
+ * 10-bit stream need no repacking and no staging copy.
+ *   Repacked equivalence: row b of out_cur is bit for bit what sy_frames_u8_pack_rows writes for the same frame repacked into
+ *       sy_frame_src's layout (dense planes, one pitch, chroma at row Hs) — all four decimate modes, mirror, both layouts, the
+ *       three Focus dtypes and the Ho x Wo canvas resize.  For SY_PIX_P010 the repacked frame is the NV12 frame of the samples'
+ *       high bytes (below).
+ *   ONE launch whose grid depends on (B, Ho, Wo, layout) only: a recorded launch serves any table contents — formats, pitches,
+ *       plane addresses and sizes are data.
+ *   SY_PIX_P010 (valid ONLY here: the other entry points keep treating 3 as an unknown format): two planes of little-endian
+ *       16-bit samples with the 10 significant bits in the HIGH bits of each word; row_stride >= 2 Ws, and the chroma row of
+ *       interleaved (U, V) words needs >= 2 Ws bytes too.  The 8-bit sample is the word's high byte (word >> 8: truncation, no
+ *       rounding, no dithering); then SY_PIX_NV12's arithmetic applies unchanged.  This is the project's own definition: no
+ *       OpenCV conversion exists to pin it against.
+ *   Reads (rows; bytes per row):  plane0 BGR / RGB: < Hs; < 3 Ws.   plane0 NV12: < Hs; < Ws.   plane0 P010: < Hs; < 2 Ws.
+ *       plane1 NV12: < Hs / 2; < Ws.   plane1 P010: < Hs / 2; < 2 Ws.  Nothing between Ws and a pitch, and nothing between the
+ *       planes, is ever read.
+ *   The host cannot see the table: the caller validates it.  A descriptor no frame can have — an unknown format, odd Hs / Ws for
+ *       NV12 / P010 or decimate 2, a pitch (either one) below the row's bytes, a negative chroma_stride — is written as a row
+ *       without a frame (the plain 114 canvas), never read through.
+ *   rows, out_cur, B, the sizes, layout and dtype: the status codes of sy_frames_u8_pack_rows.
+ *   NV12's wide-load fast path applies per row when plane0, plane1 and BOTH pitches meet its alignment (multiples of 2 for
+ *       decimate 1, of 4 for decimate 2) — decided from the chroma plane's own address and pitch; bit-identical with the generic
+ *       path, which P010 always takes. */
+enum { SY_PIX_P010 = 3 };             /* valid ONLY in sy_frames_u8_pack_surfaces */
+typedef struct sy_frame_surf {        /* 48 bytes */
+    const uint8_t* plane0;            /* BGR / RGB pixels, or the luma plane; NULL or Hs == 0: the row has no frame */
+    const uint8_t* plane1;            /* NV12 / P010: the interleaved (U, V) plane, wherever it lies.  NULL: plane0 + row_stride * Hs
+                                         (sy_frame_src's single-allocation layout).  Ignored for BGR / RGB */
+    int32_t Hs, Ws;
+    int32_t row_stride;               /* bytes between rows of plane0 */
+    int32_t chroma_stride;            /* bytes between rows of plane1; 0 = row_stride */
+    int32_t decimate, mirror, format; /* exactly as sy_frame_src */
+    int32_t reserved;                 /* 0 */
+} sy_frame_surf;
+SY_API int sy_frames_u8_pack_surfaces(const sy_frame_surf* rows, int B, int H, int W, int Ho, int Wo, int layout,
+                                      void* out_cur, int dtype, void* stream);
 
 /* Exp.preprocess's multi-scale resize on the reference's own tensor: fp32 NCHW [N, C, H, W] -> [N, C, Ho, Wo],
  * torch bilinear, align_corners=False (cfgs/l_s50_onex_dfp_tal_filp.py:161-172).  C = 3 or 6. */

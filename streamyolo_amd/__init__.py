@@ -12,10 +12,11 @@ from .model.pipe_head import PIPEHead
 from .model.tal_head import TALHead
 from .model.yolox import YOLOX
 from .postprocess import postprocess
+from .data import Surface
 from .streaming import MultiStreamDetector, StreamingDetector
 
 __all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model", "DeviceGradScaler",
-           "StreamingDetector", "MultiStreamDetector"]
+           "StreamingDetector", "MultiStreamDetector", "Surface"]
 __version__ = "0.1.0"
 
 MODEL_ZOO = {

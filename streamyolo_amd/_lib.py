@@ -22,15 +22,19 @@ ABI_VERSION = 7          # SY_ABI_VERSION of include/streamyolo_hip.h this bindi
 _ERR = {1: "bad argument", 2: "kernel launch failed", 3: "unsupported shape"}
 SY_ERR_UNSUPPORTED = 3
 PIX_BGR, PIX_RGB, PIX_NV12 = 0, 1, 2          # SY_PIX_* of include/streamyolo_hip.h
+PIX_P010 = 3                                   # decoder surfaces only (sy_frames_u8_pack_surfaces): unknown everywhere else
 PIXEL_FORMATS = {"bgr": PIX_BGR, "rgb": PIX_RGB, "nv12": PIX_NV12}
+SURFACE_FORMATS = dict(PIXEL_FORMATS, p010=PIX_P010)
 
 
-def pixel_format_code(pixel_format):
-    """"bgr" | "rgb" | "nv12" -> SY_PIX_*; ValueError for anything else."""
+def pixel_format_code(pixel_format, surfaces=False):
+    """"bgr" | "rgb" | "nv12" -> SY_PIX_*; ValueError for anything else.  surfaces=True (data.Surface, FrameSurfacesU8, a
+    detector built with surfaces=True): "p010" too."""
+    known = SURFACE_FORMATS if surfaces else PIXEL_FORMATS
     try:
-        return PIXEL_FORMATS[pixel_format]
+        return known[pixel_format]
     except (KeyError, TypeError):
-        raise ValueError("pixel_format must be one of %s, got %r" % (sorted(PIXEL_FORMATS), pixel_format)) from None
+        raise ValueError("pixel_format must be one of %s, got %r" % (sorted(known), pixel_format)) from None
 
 
 class HipLibraryError(RuntimeError):
@@ -87,6 +91,13 @@ class FrameSrc(C.Structure):
                 ("decimate", C.c_int32), ("mirror", C.c_int32), ("format", C.c_int32)]
 
 
+class FrameSurf(C.Structure):
+    """sy_frame_surf (include/streamyolo_hip.h): 48 bytes of DEVICE memory per batch row."""
+    _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32),
+                ("row_stride", C.c_int32), ("chroma_stride", C.c_int32), ("decimate", C.c_int32), ("mirror", C.c_int32),
+                ("format", C.c_int32), ("reserved", C.c_int32)]
+
+
 class StreamLevel(C.Structure):
     """sy_stream_level (include/streamyolo_hip.h)."""
     _fields_ = [("cur", C.c_void_p), ("pool", C.c_void_p), ("bs", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
@@ -124,6 +135,7 @@ SIGNATURES = {
     "sy_frames_u8_pack": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "sy_frames_u8_pack_fmt": (_I, [_P, _P, _I, _I, _I, _L, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
     "sy_frames_u8_pack_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "sy_frames_u8_pack_surfaces": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "sy_resize_bilinear_nchw": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "sy_resize_nearest": (_I, [_P, _I, _I, _I, _I, _I, _L, _P, _I, _I, _I, _L, _I, _P]),
     "sy_resize_nearest_bwd": (_I, [_P, _I, _I, _I, _I, _I, _L, _P, _I, _I, _I, _L, _I, _I, _P]),

@@ -31,8 +31,9 @@
 // pixel ONCE (the other paths call sample() once per channel).
 //   NV12 layout  ONE pitch for both planes: Hs rows of luma, then — starting at row Hs — Hs / 2 rows of interleaved chroma (U, V):
 //                the [Hs * 3 / 2, Ws] array cv2.cvtColor takes, with an optional pitch; Hs, Ws even.  Chroma of pixel (y, x) = the
-//                pair at chroma row y >> 1, byte 2 * (x >> 1) (nearest).  Surfaces whose chroma plane starts elsewhere (a padded
-//                luma height, a detached plane) are out of scope.
+//                pair at chroma row y >> 1, byte 2 * (x >> 1) (nearest).  That is sy_frames_u8_pack_fmt's and sy_frame_src's layout;
+//                a surface whose chroma plane starts elsewhere (a padded luma height, a detached plane, a pitch of its own) is
+//                described by sy_frame_surf (below).
 //   arithmetic   BT.601 limited range in the int32 fixed point OpenCV publishes for COLOR_YUV2BGR_NV12 (nv12_bgr below) — like the
 //                resize arithmetic restated from published source, PARITY UNPINNED against a cv2 binary.
 //   fast path    NV12 -> Focus layout without the canvas resize, decimate 1 | 2 (1200x1920 -> 600x960 is this case): one thread
@@ -40,6 +41,15 @@
 //                (decimate 1: 2x2 luma, one pair, three 16-bit loads) instead of 24 single-byte loads.  Taken — per launch, per
 //                row in the rows kernel — only when base pointers, pitch and image stride are multiples of the load width and ws is
 //                even; a Focus pixel not wholly inside the image takes the generic path.  Bit-identical with the generic path.
+//
+// Decoder surfaces (sy_frames_u8_pack_surfaces, sy_frame_surf).  A hardware decoder's surface is read where it lies: the row's
+// descriptor names both planes (plane1 = the chroma plane at any address, with its own pitch), so a padded luma height (1080 ->
+// 1088 rows) or a detached chroma allocation needs no repacking and no staging copy.  The NV12 sample fetch takes the chroma base,
+// the chroma pitch and a sample step (ChromaAt); the single-allocation sources fill them with cur + row_stride * Hs, row_stride
+// and step 1: ONE code path, whose bits the NV12 tests pin.  P010 (10-bit decoders: two planes of little-endian 16-bit words, the
+// significant bits on top) is the same path with a step of 2 bytes and an offset of 1: the 8-bit sample is the word's HIGH byte
+// (word >> 8: truncation, no rounding, no dithering) — the project's definition, no OpenCV conversion exists to pin it against.
+// The wide-load fast path is decided per row from BOTH planes' addresses and pitches; P010 takes the generic path only.
 #include "sy_pointwise.h"
 
 namespace {
@@ -142,20 +152,32 @@ __device__ __forceinline__ void nv12_bgr(int Y, const Chroma& k, int o[3]) {
     o[1] = sat8((y + k.g) >> 20);
     o[2] = sat8((y + k.r) >> 20);
 }
-// (B, G, R) of source pixel (sy, sx) of the NV12 image at p: luma row sy, chroma row src_h + (sy >> 1), pair 2 * (sx >> 1)
-__device__ __forceinline__ void nv12_px(const unsigned char* p, const FrameGeom& g, int sy, int sx, int o[3]) {
-    const unsigned char* uv = p + (long long)(g.src_h + (sy >> 1)) * g.row_stride + 2 * (sx >> 1);
-    nv12_bgr((int)p[(long long)sy * g.row_stride + sx], nv12_chroma((int)uv[0], (int)uv[1]), o);
+// Where the chroma plane of an NV12 image lies and how its samples are stored: the interleaved (U, V) plane at `uv` with `pitch`
+// bytes between rows; sample k of a row (either plane) is the byte at (k << sh) + sh.  sh = 0: NV12 proper.  sh = 1: P010 — 16-bit
+// little-endian words whose HIGH byte is the 8-bit sample (a step of 2 bytes and an offset of 1: the same arithmetic on other
+// bytes, not a second conversion).  The single-allocation sources fill it with p + row_stride * src_h, row_stride and the
+// literal 0, which the compiler folds: their address arithmetic is what it was.
+struct ChromaAt {
+    const unsigned char* uv;
+    int pitch;
+    int sh;
+};
+// (B, G, R) of source pixel (sy, sx) of the NV12 image whose luma plane is at p: luma row sy, chroma row sy >> 1, pair 2 * (sx >> 1)
+__device__ __forceinline__ void nv12_px(const unsigned char* p, const ChromaAt& ch, const FrameGeom& g, int sy, int sx, int o[3]) {
+    const unsigned char* uv = ch.uv + (long long)(sy >> 1) * ch.pitch + ((2 * (sx >> 1)) << ch.sh) + ch.sh;
+    nv12_bgr((int)p[(long long)sy * g.row_stride + (sx << ch.sh) + ch.sh], nv12_chroma((int)uv[0], (int)uv[1 << ch.sh]), o);
 }
 
 // frame_at for an NV12 image, all three channels of canvas pixel (y, x) at once: every source pixel is converted once and the
-// integer arithmetic of frame_at runs on the triples.  Reads stay inside src_h * 3 / 2 rows of src_w <= row_stride bytes.
-__device__ __forceinline__ void frame_at3_nv12(const unsigned char* p, const FrameGeom& g, bool mirror, int y, int x, float o[3]) {
+// integer arithmetic of frame_at runs on the triples.  Reads stay inside src_h luma rows and src_h / 2 chroma rows of
+// src_w << sh bytes each (<= the plane's pitch): nothing between src_w and a pitch, nothing between the planes.
+__device__ __forceinline__ void frame_at3_nv12(const unsigned char* p, const ChromaAt& ch, const FrameGeom& g, bool mirror, int y,
+                                               int x, float o[3]) {
     if (y >= g.hs || x >= g.ws) { o[0] = 114.0f; o[1] = 114.0f; o[2] = 114.0f; return; }
     if (mirror) x = g.ws - 1 - x;
     if (g.dec == 1) {
         int a[3];
-        nv12_px(p, g, y, x, a);
+        nv12_px(p, ch, g, y, x, a);
 #pragma unroll
         for (int c = 0; c < 3; ++c) o[c] = (float)a[c];
         return;
@@ -163,8 +185,8 @@ __device__ __forceinline__ void frame_at3_nv12(const unsigned char* p, const Fra
     if (g.dec == 0) {
         const Tap ty = frame_tap<false>(y, g.scale_y, g.src_h), tx = frame_tap<true>(x, g.scale_x, g.src_w);
         int p00[3], p01[3], p10[3], p11[3];
-        nv12_px(p, g, ty.s0, tx.s0, p00); nv12_px(p, g, ty.s0, tx.s1, p01);
-        nv12_px(p, g, ty.s1, tx.s0, p10); nv12_px(p, g, ty.s1, tx.s1, p11);
+        nv12_px(p, ch, g, ty.s0, tx.s0, p00); nv12_px(p, ch, g, ty.s0, tx.s1, p01);
+        nv12_px(p, ch, g, ty.s1, tx.s0, p10); nv12_px(p, ch, g, ty.s1, tx.s1, p11);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const int S0 = p00[c] * tx.a0 + p01[c] * tx.a1;                              // horizontal pass, scaled by 2^11
@@ -175,12 +197,13 @@ __device__ __forceinline__ void frame_at3_nv12(const unsigned char* p, const Fra
         return;
     }
     // the 2x2 source block of an exact 2x decimation shares one chroma pair: chroma row y, pair 2 x
-    const unsigned char* r0 = p + (long long)(2 * y) * g.row_stride + 2 * x;
+    const int at = ((2 * x) << ch.sh) + ch.sh, next = 1 << ch.sh;
+    const unsigned char* r0 = p + (long long)(2 * y) * g.row_stride + at;
     const unsigned char* r1 = r0 + g.row_stride;
-    const unsigned char* uv = p + (long long)(g.src_h + y) * g.row_stride + 2 * x;
-    const Chroma k = nv12_chroma((int)uv[0], (int)uv[1]);
+    const unsigned char* uv = ch.uv + (long long)y * ch.pitch + at;
+    const Chroma k = nv12_chroma((int)uv[0], (int)uv[next]);
     int a[3], b[3], c_[3], d[3];
-    nv12_bgr((int)r0[0], k, a); nv12_bgr((int)r0[1], k, b); nv12_bgr((int)r1[0], k, c_); nv12_bgr((int)r1[1], k, d);
+    nv12_bgr((int)r0[0], k, a); nv12_bgr((int)r0[next], k, b); nv12_bgr((int)r1[0], k, c_); nv12_bgr((int)r1[next], k, d);
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c] = (float)((a[c] + b[c] + c_[c] + d[c] + 2) >> 2);
 }
@@ -190,14 +213,15 @@ __device__ __forceinline__ unsigned load_u16(const unsigned char* p) { return *r
 __device__ __forceinline__ unsigned load_u32(const unsigned char* p) { return *reinterpret_cast<const unsigned int*>(p); }
 
 // The NV12 fast path: the Focus pixel (h2, w2) = output pixels (2 h2 + i, 2 w2 + j) of an image it lies wholly inside (2 h2 + 1
-// < hs, 2 w2 + 1 < ws), dec 1 | 2, ws even, p and row_stride multiples of 2 (dec 1) / 4 (dec 2) -> px[i][j][c], j counted in
+// < hs, 2 w2 + 1 < ws), dec 1 | 2, ws even, sh = 0, p, row_stride, ch.uv and ch.pitch multiples of 2 (dec 1) / 4 (dec 2) ->
+// px[i][j][c], j counted in
 // IMAGE order (mirrored: output column 2 w2 + j is px[.][1 - j] — the caller selects, so that every index here is a constant
 // and the block stays in registers).  The same integers as frame_at3_nv12 from wide loads.
-__device__ __forceinline__ void nv12_focus_block(const unsigned char* p, const FrameGeom& g, bool mirror, int h2, int w2,
-                                                 int px[2][2][3]) {
+__device__ __forceinline__ void nv12_focus_block(const unsigned char* p, const ChromaAt& ch, const FrameGeom& g, bool mirror, int h2,
+                                                 int w2, int px[2][2][3]) {
     const int xs = mirror ? g.ws - 2 - 2 * w2 : 2 * w2;             // the pair's left column in the (unmirrored) image: even
     if (g.dec == 1) {
-        const unsigned uv = load_u16(p + (long long)(g.src_h + h2) * g.row_stride + xs);
+        const unsigned uv = load_u16(ch.uv + (long long)h2 * ch.pitch + xs);
         const Chroma k = nv12_chroma((int)(uv & 255u), (int)(uv >> 8));
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -212,7 +236,7 @@ __device__ __forceinline__ void nv12_focus_block(const unsigned char* p, const F
         // output row 2 h2 + i: luma rows 4 h2 + 2 i and the next, chroma row 2 h2 + i; bytes 2 xs .. 2 xs + 3 of each
         const unsigned char* r0 = p + (long long)(4 * h2 + 2 * i) * g.row_stride + 2 * xs;
         const unsigned l0 = load_u32(r0), l1 = load_u32(r0 + g.row_stride);
-        const unsigned uv = load_u32(p + (long long)(g.src_h + 2 * h2 + i) * g.row_stride + 2 * xs);
+        const unsigned uv = load_u32(ch.uv + (long long)(2 * h2 + i) * ch.pitch + 2 * xs);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {                               // image column xs + j
             const Chroma k = nv12_chroma((int)((uv >> (16 * j)) & 255u), (int)((uv >> (16 * j + 8)) & 255u));
@@ -224,7 +248,9 @@ __device__ __forceinline__ void nv12_focus_block(const unsigned char* p, const F
         }
     }
 }
-// what the fast path needs of an image besides dec 1 | 2: even ws and every row start a multiple of the load width
+// what the fast path needs of an image besides dec 1 | 2: even ws and every row start — of BOTH planes — a multiple of the load
+// width.  addr_bits: every base address and every pitch besides g.row_stride, OR-ed (a chroma plane of its own: its address and
+// its pitch; the single-allocation layout's chroma rows start at multiples of row_stride from the base)
 __host__ __device__ inline bool nv12_fast_ok(const FrameGeom& g, unsigned long long addr_bits) {
     if ((g.dec != 1 && g.dec != 2) || (g.ws & 1)) return false;
     return ((addr_bits | (unsigned long long)g.row_stride) & (g.dec == 2 ? 3ull : 1ull)) == 0;
@@ -247,25 +273,66 @@ struct FrameSrcRGB : FrameSrc {  // the same frames in RGB order
 };
 struct FrameSrcNV12 : FrameSrc { // [B] NV12 images of src_h * 3 / 2 rows
     __device__ __forceinline__ const unsigned char* image(int n, int f) const { return img[f] + n * image_stride; }
+    __device__ __forceinline__ ChromaAt chroma(int n, int f) const {         // one pitch, chroma at row src_h
+        ChromaAt ch;
+        ch.uv = image(n, f) + (long long)g.src_h * g.row_stride; ch.pitch = g.row_stride; ch.sh = 0;
+        return ch;
+    }
     __device__ __forceinline__ bool mirrored(int n) const { return mirror != nullptr && mirror[n]; }
     __device__ __forceinline__ void at3(int n, int f, int y, int x, float o[3]) const {
         if (y >= g.hs || x >= g.ws) { o[0] = 114.0f; o[1] = 114.0f; o[2] = 114.0f; return; }
-        frame_at3_nv12(image(n, f), g, mirrored(n), y, x, o);
+        frame_at3_nv12(image(n, f), chroma(n, f), g, mirrored(n), y, x, o);
     }
 };
 
-// One batch row of sy_frames_u8_pack_rows: its descriptor, resolved.  A row without a frame — or with a descriptor no frame can
-// have (the host cannot see the table: the caller validates it) — has hs = ws = 0: the plain 114 canvas, nothing is read.
+// One batch row of sy_frames_u8_pack_rows / sy_frames_u8_pack_surfaces: its descriptor, resolved.  A row without a frame — or with
+// a descriptor no frame can have (the host cannot see the table: the caller validates it) — has hs = ws = 0: the plain 114
+// canvas, nothing is read.  fmt is SY_PIX_BGR | RGB | NV12 for the sampling: a P010 surface is NV12 with ch.sh = 1.
 struct RowSrc {
     const unsigned char* p;
     FrameGeom g;
     bool mirror;
     int fmt;                    // SY_PIX_*: scalar, like g.dec
     bool fast;                  // NV12: the image qualifies for the fast path (nv12_fast_ok)
+    ChromaAt ch;                // NV12: the chroma plane
+    __device__ __forceinline__ void clear() {
+        p = nullptr; mirror = false; fmt = SY_PIX_BGR; fast = false;
+        ch.uv = nullptr; ch.pitch = 0; ch.sh = 0;
+        g.row_stride = 0; g.hs = 0; g.ws = 0; g.dec = 1; g.src_h = 0; g.src_w = 0; g.scale_y = 1.0; g.scale_x = 1.0;
+    }
+    // a surface: the planes where they lie, each with its own pitch
+    __device__ __forceinline__ RowSrc(const sy_frame_surf* rows, int b, int H, int W) {
+        const sy_frame_surf d = rows[b];                        // one 48-byte load per workgroup (b = blockIdx.y: uniform)
+        clear();
+        if (d.plane0 == nullptr || d.Hs <= 0 || d.Ws <= 0 || d.decimate < -1 || d.decimate > 2) return;
+        if (d.format != SY_PIX_BGR && d.format != SY_PIX_RGB && d.format != SY_PIX_NV12 && d.format != SY_PIX_P010) return;
+        const bool yuv = d.format == SY_PIX_NV12 || d.format == SY_PIX_P010;
+        const int sh = d.format == SY_PIX_P010 ? 1 : 0;
+        if ((d.decimate == 2 || yuv) && ((d.Hs & 1) || (d.Ws & 1))) return;
+        const long long row_bytes = yuv ? ((long long)d.Ws << sh) : (long long)d.Ws * 3;
+        if ((long long)d.row_stride < row_bytes) return;
+        const int cpitch = d.chroma_stride != 0 ? d.chroma_stride : d.row_stride;
+        if (yuv && (d.chroma_stride < 0 || (long long)cpitch < row_bytes)) return;
+        FrameGeom r;
+        if (frame_geom(d.Hs, d.Ws, d.decimate, H, W, r) != SY_OK) return;
+        r.row_stride = d.row_stride;
+        r.dec = sy_uniform(r.dec);
+        g = r; p = d.plane0; mirror = d.mirror != 0;
+        fmt = sy_uniform(yuv ? (int)SY_PIX_NV12 : d.format);
+        if (yuv) {
+            ch.uv = d.plane1 != nullptr ? d.plane1 : d.plane0 + (long long)d.row_stride * d.Hs;
+            ch.pitch = cpitch;
+            ch.sh = sy_uniform(sh);
+            // the wide loads need BOTH planes aligned: the chroma plane's own address and pitch, not the luma's
+            const unsigned long long bits = (unsigned long long)(uintptr_t)p | (unsigned long long)(uintptr_t)ch.uv |
+                                            (unsigned long long)cpitch;
+            fast = sy_uniform(sh == 0 && nv12_fast_ok(r, bits) ? 1 : 0) != 0;
+        }
+    }
+    // sy_frame_src: one allocation, one pitch, chroma at row Hs
     __device__ __forceinline__ RowSrc(const sy_frame_src* rows, int b, int H, int W) {
         const sy_frame_src d = rows[b];                         // one 32-byte load per workgroup (b = blockIdx.y: uniform)
-        p = nullptr; mirror = false; fmt = SY_PIX_BGR; fast = false;
-        g.row_stride = 0; g.hs = 0; g.ws = 0; g.dec = 1; g.src_h = 0; g.src_w = 0; g.scale_y = 1.0; g.scale_x = 1.0;
+        clear();
         if (d.cur == nullptr || d.Hs <= 0 || d.Ws <= 0 || d.decimate < -1 || d.decimate > 2) return;
         if (d.format != SY_PIX_BGR && d.format != SY_PIX_RGB && d.format != SY_PIX_NV12) return;
         const bool nv12 = d.format == SY_PIX_NV12;
@@ -278,13 +345,15 @@ struct RowSrc {
         g = r; p = d.cur; mirror = d.mirror != 0;
         fmt = sy_uniform(d.format);
         fast = sy_uniform(nv12 && nv12_fast_ok(r, (unsigned long long)(uintptr_t)d.cur) ? 1 : 0) != 0;
+        ch.uv = d.cur + (long long)d.row_stride * d.Hs; ch.pitch = d.row_stride;
     }
     __device__ __forceinline__ float at(int, int, int c, int y, int x) const {
         return frame_at(p, g, mirror, fmt == SY_PIX_RGB ? 2 - c : c, y, x);
     }
     __device__ __forceinline__ const unsigned char* image(int, int) const { return p; }
     __device__ __forceinline__ bool mirrored(int) const { return mirror; }
-    __device__ __forceinline__ void at3(int, int, int y, int x, float o[3]) const { frame_at3_nv12(p, g, mirror, y, x, o); }
+    __device__ __forceinline__ ChromaAt chroma(int, int) const { return ch; }
+    __device__ __forceinline__ void at3(int, int, int y, int x, float o[3]) const { frame_at3_nv12(p, ch, g, mirror, y, x, o); }
 };
 
 struct PlaneSrc {               // fp32 NCHW tensor (Exp.preprocess's input)
@@ -391,7 +460,7 @@ __device__ __forceinline__ void focus_pixel3(const S& src, bool fast, int n, int
     if (fast && 2 * h2 + 1 < src.g.hs && 2 * w2 + 1 < src.g.ws) {
         int px[2][2][3];
         const bool mirror = src.mirrored(n);
-        nv12_focus_block(src.image(n, f), src.g, mirror, h2, w2, px);
+        nv12_focus_block(src.image(n, f), src.chroma(n, f), src.g, mirror, h2, w2, px);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
@@ -471,9 +540,11 @@ __global__ __launch_bounds__(kBlock) void frames_to_focus_kernel(S src, int B, i
     }
 }
 
-// ---- per-row sources (sy_frames_u8_pack_rows): blockIdx.y = the batch row, its workgroups stride over that row's outputs.
-// The grid depends on (B, Ho, Wo, layout) only: a recorded launch serves any table contents.
-__global__ __launch_bounds__(kBlock) void rows_to_nchw_kernel(const sy_frame_src* rows, int H, int W, int Ho, int Wo, float* out) {
+// ---- per-row sources (sy_frames_u8_pack_rows: D = sy_frame_src; sy_frames_u8_pack_surfaces: D = sy_frame_surf): blockIdx.y =
+// the batch row, its workgroups stride over that row's outputs.  The grid depends on (B, Ho, Wo, layout) only: a recorded
+// launch serves any table contents.
+template <typename D>
+__global__ __launch_bounds__(kBlock) void rows_to_nchw_kernel(const D* rows, int H, int W, int Ho, int Wo, float* out) {
     const int n = blockIdx.y;
     const RowSrc src(rows, n, H, W);
     const bool resize = Ho != H || Wo != W;
@@ -495,8 +566,8 @@ __global__ __launch_bounds__(kBlock) void rows_to_nchw_kernel(const sy_frame_src
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void rows_to_focus_kernel(const sy_frame_src* rows, int H, int W, int Ho, int Wo,
+template <typename T, typename D>
+__global__ __launch_bounds__(kBlock) void rows_to_focus_kernel(const D* rows, int H, int W, int Ho, int Wo,
                                                                typename T::elem* out) {
     const int n = blockIdx.y;
     const RowSrc src(rows, n, H, W);
@@ -603,22 +674,36 @@ extern "C" int sy_frames_u8_pack(const uint8_t* cur, const uint8_t* sup, int B, 
                                  out_sup, dtype, SY_PIX_BGR, stream);
 }
 
-extern "C" int sy_frames_u8_pack_rows(const sy_frame_src* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,
-                                      int dtype, void* stream) {
+namespace {
+
+template <typename D>
+int rows_pack_launch(const D* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur, int dtype, void* stream) {
     if (rows == nullptr || out_cur == nullptr || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return SY_ERR_ARG;
     if (dtype != SY_DT_BF16 && dtype != SY_DT_F16 && dtype != SY_DT_F32) return SY_ERR_ARG;
     if (B > 65535 || (long long)3 * Ho * Wo > (1LL << 30)) return SY_ERR_UNSUPPORTED;      // grid.y; 32-bit per-row indices + stride
     if (layout == SY_FRAMES_NCHW) {
         if (dtype != SY_DT_F32) return SY_ERR_ARG;
-        SY_LAUNCH(rows_to_nchw_kernel, rows_grid((long long)3 * Ho * Wo, B), dim3(kBlock), 0, stream, rows, H, W, Ho, Wo,
+        SY_LAUNCH((rows_to_nchw_kernel<D>), rows_grid((long long)3 * Ho * Wo, B), dim3(kBlock), 0, stream, rows, H, W, Ho, Wo,
                   (float*)out_cur);
         return SY_LAUNCH_OK() == 0 ? SY_OK : SY_ERR_LAUNCH;
     }
     if (layout != SY_FRAMES_FOCUS) return SY_ERR_ARG;
     if ((Ho & 1) || (Wo & 1)) return SY_ERR_ARG;
     const dim3 grid = rows_grid((long long)(Ho / 2) * (Wo / 2), B);
-    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((rows_to_focus_kernel<T>), grid, dim3(kBlock), 0, stream, rows, H, W, Ho, Wo,
+    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((rows_to_focus_kernel<T, D>), grid, dim3(kBlock), 0, stream, rows, H, W, Ho, Wo,
                                        (typename T::elem*)out_cur));
+}
+
+}  // namespace
+
+extern "C" int sy_frames_u8_pack_rows(const sy_frame_src* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,
+                                      int dtype, void* stream) {
+    return rows_pack_launch(rows, B, H, W, Ho, Wo, layout, out_cur, dtype, stream);
+}
+
+extern "C" int sy_frames_u8_pack_surfaces(const sy_frame_surf* rows, int B, int H, int W, int Ho, int Wo, int layout, void* out_cur,
+                                          int dtype, void* stream) {
+    return rows_pack_launch(rows, B, H, W, Ho, Wo, layout, out_cur, dtype, stream);
 }
 
 extern "C" int sy_resize_bilinear_nchw(const float* in, int N, int C, int H, int W, float* out, int Ho, int Wo,

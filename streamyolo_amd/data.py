@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import PIX_NV12, pixel_format_code
+from ._lib import PIX_NV12, PIX_P010, pixel_format_code
 
 
 class FramePairsU8:
@@ -154,6 +154,9 @@ class FrameRowsU8(FramePairsU8):
         rows.set_row(0, frame_a); rows.set_row(1, None); rows.upload()
         model(rows, mode="on_pipe")             # or rows.to_nchw(), rows.pack_focus(view)"""
 
+    _DESC = _ROW_DTYPE                                               # one table row (FrameSurfacesU8: sy_frame_surf)
+    _KEY = "rows"
+
     def __init__(self, batch, max_frame_hw, canvas, device, out_size=None):
         self.batch = int(batch)
         self.max_frame_hw = (int(max_frame_hw[0]), int(max_frame_hw[1]))
@@ -163,21 +166,22 @@ class FrameRowsU8(FramePairsU8):
         dev = torch.device(device)
         B = self.batch
         self.arena = torch.zeros((B, self.max_frame_hw[0] * self.max_frame_hw[1] * 3), dtype=torch.uint8, device=dev)
-        self._buf = torch.zeros(36 * B, dtype=torch.uint8, device=dev)
-        self.table = self._buf[:32 * B]                              # B sy_frame_src
-        self.divisor = self._buf[32 * B:].view(torch.float32)        # [B]: boxes of row b / divisor[b] = camera coordinates
-        self._rows = np.zeros(B, dtype=_ROW_DTYPE)                   # host master copy, edited by set_row
+        D = self._DESC.itemsize                                      # 32: sy_frame_src
+        self._buf = torch.zeros((D + 4) * B, dtype=torch.uint8, device=dev)
+        self.table = self._buf[:D * B]                               # B sy_frame_src
+        self.divisor = self._buf[D * B:].view(torch.float32)         # [B]: boxes of row b / divisor[b] = camera coordinates
+        self._rows = np.zeros(B, dtype=self._DESC)                   # host master copy, edited by set_row
         self._div = np.ones(B, dtype=np.float32)
         # a ring of host mirrors: an upload still in flight keeps reading its mirror while the next tick's rows are written
-        self._ring = [torch.zeros(36 * B, dtype=torch.uint8) for _ in range(4 if dev.type == "cuda" else 1)]
+        self._ring = [torch.zeros((D + 4) * B, dtype=torch.uint8) for _ in range(4 if dev.type == "cuda" else 1)]
         if dev.type == "cuda":
             self._ring = [h.pin_memory() for h in self._ring]
         self._done = [None] * len(self._ring)
         self._at = 0
         # what the plans look at (FramePairsU8's surface): the arena stands for the frames, the table is part of the tape key
         self.cur, self.sup, self.mirror = self.arena, None, None
-        self.decimate = ("rows", self.table.data_ptr())
-        self.pixel_format = "rows"                                   # per row, in the table
+        self.decimate = (self._KEY, self.table.data_ptr())
+        self.pixel_format = self._KEY                                # per row, in the table
         self.upload()
 
     def set_row(self, b, frame, mirror=False, decimate=None, divisor=None, pixel_format="bgr"):
@@ -190,7 +194,7 @@ class FrameRowsU8(FramePairsU8):
         if not 0 <= b < self.batch:
             raise ValueError("FrameRowsU8: row %r of %d" % (b, self.batch))
         if frame is None:
-            self._rows[b] = (0, 0, 0, 0, 1, 0, 0)
+            self._rows[b] = self._staged_row(0, 0, 0, 0, 1, 0, 0)
             self._div[b] = 1.0
             return
         f = torch.as_tensor(frame)
@@ -214,9 +218,14 @@ class FrameRowsU8(FramePairsU8):
             self.arena[b, :hs * ws * 3 // 2].view(hs * 3 // 2, ws).copy_(f, non_blocking=True)
         else:
             self.arena[b, :hs * ws * 3].view(hs, ws, 3).copy_(f, non_blocking=True)
-        self._rows[b] = (self.arena.data_ptr() + b * self.arena.stride(0), hs, ws, ws if fmt == PIX_NV12 else ws * 3, dec,
-                         1 if mirror else 0, fmt)
+        self._rows[b] = self._staged_row(self.arena.data_ptr() + b * self.arena.stride(0), hs, ws,
+                                         ws if fmt == PIX_NV12 else ws * 3, dec, 1 if mirror else 0, fmt)
         self._div[b] = divisor
+
+    @staticmethod
+    def _staged_row(ptr, hs, ws, row_stride, dec, mirror, fmt):
+        """One table row of a frame in the single-allocation layout (all zeros, decimate 1: no frame)."""
+        return (ptr, hs, ws, row_stride, dec, mirror, fmt)
 
     def upload(self):
         """The rows as set_row left them -> the device table: ONE non-blocking copy on the current stream."""
@@ -224,9 +233,9 @@ class FrameRowsU8(FramePairsU8):
         if self._done[self._at] is not None:
             self._done[self._at].synchronize()                       # (only when the device is a whole ring of ticks behind)
         host = self._ring[self._at].numpy()
-        B = self.batch
-        host[:32 * B] = self._rows.view(np.uint8)
-        host[32 * B:] = self._div.view(np.uint8)
+        n = self._DESC.itemsize * self.batch
+        host[:n] = self._rows.view(np.uint8)
+        host[n:] = self._div.view(np.uint8)
         self._buf.copy_(self._ring[self._at], non_blocking=True)
         if self._buf.is_cuda:
             ev = self._done[self._at] or torch.cuda.Event()
@@ -246,13 +255,165 @@ class FrameRowsU8(FramePairsU8):
     def to_nchw(self):
         """fp32 [batch, 3, Ho, Wo] of the rows last uploaded."""
         out = torch.empty(tuple(self.shape), dtype=torch.float32, device=self.device)
-        ops.frames_u8_pack_rows(self.table, self.batch, self.canvas, self.out_size, out)
+        self._pack(out)
         return out
 
     def pack_focus(self, cur_view, sup_view=None):
         """Write the stem operand (Focus-packed NHWC16 View of the plan) straight from the rows last uploaded."""
         assert sup_view is None
-        ops.frames_u8_pack_rows(self.table, self.batch, self.canvas, self.out_size, cur_view)
+        self._pack(cur_view)
+
+    def _pack(self, out):
+        ops.frames_u8_pack_rows(self.table, self.batch, self.canvas, self.out_size, out)
+
+
+_INT16 = tuple(t for t in (torch.int16, getattr(torch, "uint16", None)) if t is not None)
+
+
+class Surface:
+    """One camera frame as a hardware decoder hands it over, to be read WHERE IT LIES (FrameSurfacesU8, sy_frame_surf): no copy
+    into a staging arena, no repacking of a padded surface.
+
+    planes, by pixel_format:
+      "bgr" / "rgb"  one uint8 tensor [Hs, Ws, 3] with strides (pitch, 3, 1), pitch >= 3 Ws (a column slice of a wider image);
+      "nv12"         (luma [Hs, Ws], chroma [Hs/2, Ws]) uint8, strides (pitch, 1) each; Hs, Ws even; the chroma rows hold the
+                     interleaved (U, V) pairs.  The two pitches may differ, the planes may be views of one allocation (a luma
+                     plane padded to 1088 rows, chroma behind it) or separate tensors;
+      "p010"         the same two planes of little-endian 16-bit samples with the significant bits on top, as byte views
+                     [Hs, 2 Ws] / [Hs/2, 2 Ws] or as 16-bit integer tensors [Hs, Ws] / [Hs/2, Ws].  The pipeline uses each
+                     word's high byte (word >> 8, truncation) as the 8-bit sample and then treats the frame as NV12 — the
+                     project's own definition, see DESIGN.md.
+    ValueError for anything else.  The tensors are kept (not copied): whoever owns them must not rewrite them until the tick
+    that reads them has run on the device (FrameSurfacesU8)."""
+
+    def __init__(self, planes, pixel_format):
+        fmt = pixel_format_code(pixel_format, surfaces=True)
+        planes = (planes,) if isinstance(planes, torch.Tensor) else tuple(planes)
+        yuv = fmt in (PIX_NV12, PIX_P010)
+        if len(planes) != (2 if yuv else 1) or not all(isinstance(p, torch.Tensor) for p in planes):
+            raise ValueError("Surface: %r takes %s, got %d object(s)" % (pixel_format, "(luma, chroma) tensors" if yuv else "one tensor",
+                                                                        len(planes)))
+        if fmt == PIX_P010:                                          # 16-bit samples -> the bytes they are stored as
+            planes = tuple(self._bytes(p) for p in planes)
+        for p in planes:
+            if p.dtype != torch.uint8 or p.dim() != (2 if yuv else 3) or p.stride(-1) != 1 or p.shape[0] < 1 or p.shape[1] < 1:
+                raise ValueError("Surface: %r planes are uint8 %s with innermost stride 1, got %s %s strides %s"
+                                 % (pixel_format, "[rows, bytes]" if yuv else "[Hs, Ws, 3]", p.dtype, tuple(p.shape), p.stride()))
+            if p.device != planes[0].device:
+                raise ValueError("Surface: planes on %s and %s" % (planes[0].device, p.device))
+        y = planes[0]
+        if yuv:
+            step = 2 if fmt == PIX_P010 else 1
+            hs, row_bytes = int(y.shape[0]), int(y.shape[1])
+            ws = row_bytes // step
+            if hs % 2 or ws % 2 or row_bytes != ws * step:
+                raise ValueError("Surface: %r frames have even sizes, got a luma plane of %d rows of %d bytes" % (pixel_format, hs, row_bytes))
+            if tuple(planes[1].shape) != (hs // 2, row_bytes):
+                raise ValueError("Surface: a %s luma plane %s goes with a chroma plane %s, got %s"
+                                 % (pixel_format, tuple(y.shape), (hs // 2, row_bytes), tuple(planes[1].shape)))
+        else:
+            hs, ws, row_bytes = int(y.shape[0]), int(y.shape[1]), 3 * int(y.shape[1])
+            if y.shape[2] != 3 or y.stride(1) != 3:
+                raise ValueError("Surface: %r pixels are [Hs, Ws, 3] with strides (pitch, 3, 1), got %s strides %s"
+                                 % (pixel_format, tuple(y.shape), y.stride()))
+        # (torch leaves the stride of a one-row dimension undefined: such a plane has no second row to find)
+        pitches = tuple(int(p.stride(0)) if p.shape[0] > 1 else max(int(p.stride(0)), row_bytes) for p in planes)
+        if min(pitches) < row_bytes or max(pitches) >= 1 << 31:
+            raise ValueError("Surface: pitches %r for rows of %d bytes" % (pitches, row_bytes))
+        self.planes, self.pixel_format, self.format = planes, pixel_format, fmt
+        self.hw, self.pitch, self.chroma_pitch = (hs, ws), pitches[0], pitches[-1] if yuv else 0
+
+    @staticmethod
+    def _bytes(p):
+        if p.dtype in _INT16 and p.dim() == 2 and p.stride(1) == 1:
+            return p.view(torch.uint8)                               # [rows, Ws] words -> [rows, 2 Ws] bytes, little endian
+        return p
+
+    @classmethod
+    def from_buffer(cls, buf, hs, ws, pixel_format, chroma_row=None):
+        """The usual single-buffer surface: `buf` uint8 [rows, pitch]; the frame's rows start at row 0 and — "nv12" / "p010" —
+        its chroma rows at row `chroma_row` (default hs; a decoder that pads the luma plane: the padded height)."""
+        fmt = pixel_format_code(pixel_format, surfaces=True)
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 2:
+            raise ValueError("Surface.from_buffer: buf is a uint8 tensor [rows, pitch]")
+        hs, ws = int(hs), int(ws)
+        row_bytes = ws * (1 if fmt == PIX_NV12 else 2 if fmt == PIX_P010 else 3)
+        if fmt not in (PIX_NV12, PIX_P010):
+            if hs < 1 or ws < 1 or buf.shape[0] < hs or buf.shape[1] < row_bytes:
+                raise ValueError("Surface.from_buffer: a %dx%d %s frame in a buffer %s" % (hs, ws, pixel_format, tuple(buf.shape)))
+            return cls(buf[:hs, :row_bytes].unflatten(1, (ws, 3)), pixel_format)
+        c0 = hs if chroma_row is None else int(chroma_row)
+        if hs < 2 or ws < 2 or hs % 2 or c0 < hs or buf.shape[0] < c0 + hs // 2 or buf.shape[1] < row_bytes:
+            raise ValueError("Surface.from_buffer: a %dx%d %s frame with chroma at row %d in a buffer %s"
+                             % (hs, ws, pixel_format, c0, tuple(buf.shape)))
+        return cls((buf[:hs, :row_bytes], buf[c0:c0 + hs // 2, :row_bytes]), pixel_format)
+
+    @property
+    def device(self):
+        return self.planes[0].device
+
+
+# sy_frame_surf (include/streamyolo_hip.h), one per batch row
+_SURF_DTYPE = np.dtype([("plane0", "<u8"), ("plane1", "<u8"), ("Hs", "<i4"), ("Ws", "<i4"), ("row_stride", "<i4"),
+                        ("chroma_stride", "<i4"), ("decimate", "<i4"), ("mirror", "<i4"), ("format", "<i4"), ("reserved", "<i4")])
+assert _SURF_DTYPE.itemsize == 48
+
+
+class FrameSurfacesU8(FrameRowsU8):
+    """FrameRowsU8 whose rows may be decoder surfaces read in place: the table holds sy_frame_surf descriptors (both planes'
+    addresses and pitches) and the launch is sy_frames_u8_pack_surfaces — still ONE launch for any mix of rows.
+
+    set_row(b, Surface(...)) writes the planes' addresses and pitches into the table and copies NOTHING: the arena is not touched.
+    set_row with a plain array or tensor stages it into the arena exactly as FrameRowsU8 does (a descriptor with plane1 = NULL);
+    "p010" frames come as a Surface only.  upload / to_nchw / pack_focus / resized are FrameRowsU8's.
+
+    Lifetime.  The object keeps a reference to a row's plane tensors until that row is set again, so their memory cannot be
+    freed under a pending launch.  What it cannot do is stop the owner from WRITING to them: a surface must not be rewritten
+    (handed back to the decoder) until the tick that reads it has run on the device — record an event on the tick's stream after
+    the tick and wait for it, as with any zero-copy input.
+
+        rows = FrameSurfacesU8(batch, (Hmax, Wmax), canvas, device)
+        rows.set_row(0, Surface.from_buffer(decoded, 1080, 1920, "nv12", chroma_row=1088)); rows.set_row(1, frame_b)
+        rows.upload(); model(rows, mode="on_pipe")"""
+
+    _DESC = _SURF_DTYPE
+    _KEY = "surfaces"
+
+    def __init__(self, batch, max_frame_hw, canvas, device, out_size=None):
+        self._held = [None] * int(batch)                             # row -> the plane tensors its descriptor points into
+        super().__init__(batch, max_frame_hw, canvas, device, out_size)
+
+    @staticmethod
+    def _staged_row(ptr, hs, ws, row_stride, dec, mirror, fmt):
+        return (ptr, 0, hs, ws, row_stride, 0, dec, mirror, fmt, 0)  # plane1 = NULL: chroma at row hs, the same pitch
+
+    def _pack(self, out):
+        ops.frames_u8_pack_surfaces(self.table, self.batch, self.canvas, self.out_size, out)
+
+    def set_row(self, b, frame, mirror=False, decimate=None, divisor=None, pixel_format=None):
+        """FrameRowsU8.set_row; `frame` may also be a Surface (pixel_format None or the surface's own), which must live on this
+        object's device.  ValueError — before anything is written — for what the object or the kernel would refuse."""
+        if not isinstance(frame, Surface):
+            super().set_row(b, frame, mirror, decimate, divisor, "bgr" if pixel_format is None else pixel_format)
+            self._held[b] = None
+            return
+        if not 0 <= b < self.batch:
+            raise ValueError("FrameSurfacesU8: row %r of %d" % (b, self.batch))
+        if pixel_format is not None and pixel_format != frame.pixel_format:
+            raise ValueError("FrameSurfacesU8: a %r surface given as %r" % (frame.pixel_format, pixel_format))
+        if frame.device != self.arena.device:
+            raise ValueError("FrameSurfacesU8: a surface on %s cannot be read in place from %s (copy it, or pass the array to have "
+                             "it staged)" % (frame.device, self.arena.device))
+        dec, r = row_geometry(frame.hw, self.canvas, decimate)
+        if divisor is None:
+            if r is None:
+                raise ValueError("FrameSurfacesU8: decimate -1 has no single ratio, pass divisor")
+            divisor = r
+        yuv = len(frame.planes) == 2
+        self._rows[b] = (frame.planes[0].data_ptr(), frame.planes[1].data_ptr() if yuv else 0, frame.hw[0], frame.hw[1],
+                         frame.pitch, frame.chroma_pitch, dec, 1 if mirror else 0, frame.format, 0)
+        self._div[b] = divisor
+        self._held[b] = frame.planes
 
 
 def preprocess(inputs, targets, tsize, input_size):

@@ -278,6 +278,27 @@ def frames_u8_pack_rows(table, B, canvas, out_size, out):
           "sy_frames_u8_pack_rows")
 
 
+def frames_u8_pack_surfaces(table, B, canvas, out_size, out):
+    """frames_u8_pack_rows over decoder surfaces read where they lie: `table` = uint8 device tensor holding B sy_frame_surf
+    descriptors (48 bytes each: both planes' addresses and pitches; data.FrameSurfacesU8 fills and validates them).  out as
+    frames_u8_pack_rows.  One launch whose shape does not depend on the table."""
+    assert table.dtype == torch.uint8 and table.is_contiguous() and table.numel() >= 48 * B and table.data_ptr() % 8 == 0
+    H, W = canvas
+    Ho, Wo = out_size
+    if isinstance(out, View):
+        layout, dt = FRAMES_FOCUS, out.dtype
+        assert out.C == 16 and out.ld == 16 and out.c_off == 0 and (out.N, out.H, out.W) == (B, Ho // 2, Wo // 2)
+        assert out.buf.device == table.device
+        po = out.ptr()
+    else:
+        layout, dt = FRAMES_NCHW, DT_F32
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.device == table.device
+        assert tuple(out.shape) == (B, 3, Ho, Wo)
+        po = out.data_ptr()
+    check(_lib.lib().sy_frames_u8_pack_surfaces(table.data_ptr(), B, H, W, Ho, Wo, layout, po, dt, stream_of(table)),
+          "sy_frames_u8_pack_surfaces")
+
+
 def resize_bilinear_nchw(x, out):
     """fp32 NCHW [N, 3|6, H, W] -> out [N, C, Ho, Wo]: torch bilinear, align_corners=False (Exp.preprocess)."""
     assert x.dtype == torch.float32 and x.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()

@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 from ._lib import PIX_NV12, pixel_format_code
-from .data import FramePairsU8, FrameRowsU8, row_geometry
+from .data import FramePairsU8, FrameRowsU8, FrameSurfacesU8, Surface, row_geometry
 from .postprocess import postprocess_device
 
 
@@ -45,6 +45,15 @@ def frame_shape(frame_hw, pixel_format="bgr"):
     return (h * 3 // 2, w)
 
 
+def _stream_shape(frame_hw, pixel_format, surfaces):
+    """frame_shape() for a stream of a detector; surfaces=True knows "p010" too, whose frames come as data.Surface only: None."""
+    if surfaces and pixel_format == "p010":
+        if int(frame_hw[0]) % 2 or int(frame_hw[1]) % 2:
+            raise ValueError("P010 frames have even sizes, got %dx%d" % (int(frame_hw[0]), int(frame_hw[1])))
+        return None
+    return frame_shape(frame_hw, pixel_format)
+
+
 def _parse(det, cnt, in_scale):
     """Kept rows [n, 7] of image 0 -> the reference's (bboxes / in_scale, scores, labels, None) host arrays."""
     n = int(cnt[0])
@@ -62,7 +71,11 @@ class StreamingDetector:
     axis stretched on its own): with in_scale = 0.5 on even frames that is the exact 2x decimation, with any other in_scale
     OpenCV's fixed-point bilinear resize — both done on the device together with the Focus packing (sy_frames_u8_pack,
     csrc/input_pipeline.hip).  pixel_format "rgb" / "nv12": the frames arrive in that format (frame_shape()) and the same
-    launch converts them, as cv2.cvtColor in front of the loop would."""
+    launch converts them, as cv2.cvtColor in front of the loop would.
+
+    Every frame is copied into the detector's own slot: its tape carries the frame pointer by value, so a per-frame pointer cannot
+    ride in it.  A single camera whose decoder surfaces should be read in place (data.Surface) uses
+    MultiStreamDetector(batch=1, surfaces=True), whose pointers are table data."""
 
     def __init__(self, model, frame_hw, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65, dtype="fp16",
                  device="cuda", pixel_format="bgr"):
@@ -152,18 +165,30 @@ class MultiStreamDetector:
         ring, side = det.open(), det.open(frame_hw=(1550, 2048))
         (boxes_r, ...), (boxes_s, ...) = det([ring_frame, side_frame], [ring, side])
 
+    surfaces=True is the mixed mode over data.FrameSurfacesU8 (max_frame_hw defaults to frame_hw): a tick's frames may mix plain
+    arrays (staged, as above) and data.Surface objects — decoder output read where it lies, padded or split planes included,
+    nothing copied — and open(pixel_format="p010") is accepted (10-bit decoders; Surface only).  The pack launch is
+    sy_frames_u8_pack_surfaces, still one per tick and the one tape.  A Surface must stay unwritten until its tick has run on the
+    device (FrameSurfacesU8).
+
+        det = MultiStreamDetector(model, (1080, 1920), batch=4, surfaces=True); det.warm_up()
+        cam = det.open(pixel_format="nv12")
+        det([Surface.from_buffer(decoded, 1080, 1920, "nv12", chroma_row=1088)], [cam])
+
     Which frames go into a tick is the caller's scheduling policy."""
 
     def __init__(self, model, frame_hw, max_streams=16, batch=8, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65,
-                 dtype="fp16", device="cuda", max_frame_hw=None, pixel_format="bgr"):
-        self.pixel_format = pixel_format
-        self._frame_shape = frame_shape(frame_hw, pixel_format)      # (ValueError before anything is built)
+                 dtype="fp16", device="cuda", max_frame_hw=None, pixel_format="bgr", surfaces=False):
+        self.pixel_format, self.surfaces = pixel_format, bool(surfaces)
+        self._frame_shape = _stream_shape(frame_hw, pixel_format, self.surfaces)     # (ValueError before anything is built)
         if int(batch) < 1 or int(max_streams) < 1:
             raise ValueError("MultiStreamDetector: batch and max_streams must be positive")
         if max_frame_hw is not None:
             max_frame_hw = (int(max_frame_hw[0]), int(max_frame_hw[1]))
             if max_frame_hw[0] < int(frame_hw[0]) or max_frame_hw[1] < int(frame_hw[1]):
                 raise ValueError("MultiStreamDetector: max_frame_hw %r is below frame_hw %r" % (max_frame_hw, tuple(frame_hw)))
+        elif self.surfaces:
+            max_frame_hw = (int(frame_hw[0]), int(frame_hw[1]))
         self.max_frame_hw = max_frame_hw
         self.model = model.to(device).eval().set_compute_dtype(dtype)
         self.device = torch.device(device)
@@ -187,7 +212,7 @@ class MultiStreamDetector:
         else:
             # mixed mode: a byte arena per row and the per-row descriptor table (rows without a frame are the plain canvas)
             self._stage = None
-            self._in = FrameRowsU8(self.batch, self.max_frame_hw, self.canvas, self.device)
+            self._in = (FrameSurfacesU8 if self.surfaces else FrameRowsU8)(self.batch, self.max_frame_hw, self.canvas, self.device)
         self._geom = {}                                          # mixed mode: open stream id -> (frame hw, decimate, box divisor)
         self._fmt = {}                                           # open stream id -> (pixel format, shape of its frames)
         split_k = str(dtype) not in ("fp32", "torch.float32") and os.environ.get("STREAMYOLO_STREAM_SPLITK", "1") != "0"
@@ -209,7 +234,7 @@ class MultiStreamDetector:
         geom = (self.frame_hw, self.decimate, self.in_scale)
         if pixel_format is None:
             pixel_format = self.pixel_format
-        pixel_format_code(pixel_format)
+        pixel_format_code(pixel_format, surfaces=self.surfaces)
         if self.max_frame_hw is None and pixel_format != self.pixel_format:
             raise ValueError("MultiStreamDetector: a uniform detector serves %r frames only (open(pixel_format=%r)); build it "
                              "with max_frame_hw for per-stream formats" % (self.pixel_format, pixel_format))
@@ -221,7 +246,7 @@ class MultiStreamDetector:
                 raise ValueError("MultiStreamDetector: a %dx%d camera is above max_frame_hw %dx%d" % (hw + self.max_frame_hw))
             decimate, r = row_geometry(hw, self.canvas)          # (ValueError: nothing of the frame is left on the canvas)
             geom = (hw, decimate, r)
-        shape = frame_shape(geom[0], pixel_format)               # (ValueError: an odd NV12 size)
+        shape = _stream_shape(geom[0], pixel_format, self.surfaces)      # (ValueError: an odd NV12 / P010 size)
         if not self._free:
             raise RuntimeError("MultiStreamDetector: all %d streams are open" % self.max_streams)
         sid = self._next_id
@@ -281,8 +306,18 @@ class MultiStreamDetector:
                 raise ValueError("MultiStreamDetector: a stream id appears twice in one tick: %r" % (tick,))
         fs = []
         for f, sid in zip(frames, sids):
-            f = torch.as_tensor(f)
             fmt, shape = self._fmt[sid]                          # its stream's format and camera size (uniform mode: frame_hw)
+            if isinstance(f, Surface):
+                if not self.surfaces:
+                    raise ValueError("MultiStreamDetector: a Surface needs a detector built with surfaces=True")
+                if f.pixel_format != fmt or f.hw != self._geom[sid][0] or f.device != self._in.device:
+                    raise ValueError("MultiStreamDetector: stream %r takes %s surfaces of %dx%d on %s, got %s %dx%d on %s"
+                                     % ((sid, fmt) + self._geom[sid][0] + (self._in.device, f.pixel_format) + f.hw + (f.device,)))
+                fs.append(f)
+                continue
+            if shape is None:
+                raise ValueError("MultiStreamDetector: frames of stream %r (%s) come as data.Surface" % (sid, fmt))
+            f = torch.as_tensor(f)
             if f.dtype != torch.uint8 or tuple(f.shape) != shape:
                 raise ValueError("MultiStreamDetector: frames of stream %r (%s) must be uint8 %s, got %s %s"
                                  % (sid, fmt, list(shape), f.dtype, tuple(f.shape)))
@@ -323,7 +358,7 @@ class MultiStreamDetector:
         return res if self._stage is not None else res + (self._in.divisor,)
 
     def __call__(self, frames, sids):
-        """n camera frames (uint8 [H, W, 3] arrays or tensors) and the ids of their streams -> n (bboxes, scores, labels, None)
+        """n camera frames (uint8 [H, W, 3] arrays or tensors; surfaces=True: data.Surface too) and the ids of their streams -> n (bboxes, scores, labels, None)
         host tuples in the order given, each what StreamingDetector returns for that frame.  n > batch: consecutive ticks.
         Every tick ends with the device synchronised by the copy of its counts and kept rows."""
         fs, sids = self._check(frames, sids), list(sids)

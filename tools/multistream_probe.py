@@ -23,6 +23,14 @@ detector's tick at the same batch, measured in the same process, alternating: `b
 over best round) and the per-round times of both (`ms_rounds`, `bgr_ms_rounds`: the spread the ratio has to be read against).
 
     python tools/multistream_probe.py --pixel-format nv12 --batches 1,8 --out profiles/r09/multistream_probe_nv12.json
+
+--surfaces 1: the mixed-mode tick (max_frame_hw; every stream a --pixel-format camera of the frame size) timed two ways in one
+process, alternating: `staged` — the frames are plain tensors, copied into the detector's arena every tick — and `surfaces` —
+MultiStreamDetector(surfaces=True) with every row a data.Surface read where it lies (no copy).  Rows carry
+`staged_ms_per_tick`, `surfaces_ms_per_tick`, the per-round times of both and `surfaces_over_staged`.  --staged-only 1 leaves
+the second detector out (the same measurement on a tree that has no surfaces).
+
+    python tools/multistream_probe.py --surfaces 1 --pixel-format nv12 --batches 1,8
 """
 import argparse
 import json
@@ -51,6 +59,9 @@ def main():
     ap.add_argument("--mixed", type=int, default=0, help="1: mixed-mode detector, row cameras cycling through three sizes")
     ap.add_argument("--pixel-format", default="bgr", choices=["bgr", "rgb", "nv12"],
                     help="the format the cameras deliver; not bgr: timed beside the BGR tick of the same batch")
+    ap.add_argument("--surfaces", type=int, default=0,
+                    help="1: the mixed-mode tick of --pixel-format cameras, staged beside every row a Surface read in place")
+    ap.add_argument("--staged-only", type=int, default=0, help="with --surfaces 1: only the staged tick (runs on older trees)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -134,6 +145,43 @@ def main():
         res["pixel_format"] = fmt
         fmt_frames = [bgr_to_nv12(f) if fmt == "nv12" else f.flip(-1).contiguous() for f in frames]
     alt = bool(args.mixed) or fmt != "bgr"                       # a second detector of the batch is timed beside the uniform BGR one
+
+    if args.surfaces:
+        if args.mixed:
+            ap.error("--surfaces and --mixed are separate measurements")
+        from streamyolo_amd.streaming import MultiStreamDetector
+        res.update({"pixel_format": fmt, "surfaces": True})
+        cam = frames if fmt == "bgr" else fmt_frames
+        for B in batches:
+            kw = dict(max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+            staged = MultiStreamDetector(model, hw, max_frame_hw=hw, **kw)
+            staged.warm_up(args.warmup)
+            s_sids = [staged.open(pixel_format=fmt) for _ in range(B)]
+            ticks = {"staged": lambda: staged.detect_device(cam[:B], s_sids)}
+            if not args.staged_only:
+                from streamyolo_amd.data import Surface
+                inplace = MultiStreamDetector(model, hw, surfaces=True, **kw)
+                inplace.warm_up(args.warmup)
+                i_sids = [inplace.open(pixel_format=fmt) for _ in range(B)]
+                surfs = [Surface((f[:hw[0]], f[hw[0]:]), fmt) if fmt == "nv12" else Surface(f, fmt) for f in cam[:B]]
+                ticks["surfaces"] = lambda: inplace.detect_device(surfs, i_sids)
+            rounds = {k: [] for k in ticks}
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                for k, fn in ticks.items():
+                    fn()                                         # (untimed: first rows done; a tape re-recorded after a switch)
+                    rounds[k].append(timed(fn, args.ticks)[0])
+            row = {"batch": B, "active": B, "pixel_format": fmt}
+            for k, v in rounds.items():
+                row.update({k + "_ms_per_tick": min(v), k + "_ms_rounds": v, k + "_spread_over_rounds": (max(v) - min(v)) / min(v)})
+            if "surfaces" in rounds:
+                row["surfaces_over_staged"] = min(rounds["surfaces"]) / min(rounds["staged"])
+            res["rows"].append(row)
+            emit()
+            del ticks, staged
+            if not args.staged_only:
+                del inplace, surfs
+        print(emit())
+        return
 
     if args.baseline_only:
         single_tick(1)
