@@ -510,6 +510,59 @@ typedef struct sy_stream_level {
 SY_API int sy_stream_state_scatter(const sy_stream_level* levels, int n_levels, int n_slots, int B, const int32_t* row_slot,
                                    int dtype, void* stream);
 
+/* ---- per-stream tracking and forecasting behind the NMS (many cameras, one tick) -----------------------------------
+ * Stand in, per batch row, for the reference's streaming post-processing step (sAP/forecast/pps_forecast_kf.py with
+ * --forecast-before-assoc, sAP/track/__init__.py::iou_assoc, sAP/forecast/__init__.py::extrap_clean_up): a constant-velocity
+ * Kalman filter per track over ltwh boxes in camera coordinates, greedy IoU association of a tick's detections (in the order
+ * sy_postprocess delivers them: descending score) with the predicted tracks of the same class, and the clipped forecast of
+ * every track `horizon` frames ahead.  A camera's tracks live in slot s of the pools of sy_track_state, the slot of a batch
+ * row is row_slot[b] as in sy_stream_state_gather (the same DEVICE tables; row_first[b] != 0 restarts the slot: no tracks,
+ * ids from 0), and what varies per tick and row is the DEVICE table `ticks`.  At most max_tracks detections of a row are
+ * used; the ones beyond (the lowest scores) are dropped.  Fresh ids are next_id++ in detection order (the reference advances
+ * its counter twice when nothing matches).  All arithmetic fp32, no atomics: bit-reproducible.  Added to ABI 7 (nothing
+ * existing changed). */
+typedef struct sy_track_tick {      /* 32 bytes of DEVICE memory per batch row                                           */
+    int32_t dt_frames;              /* frames since this stream's previous tick (ignored where row_first is set)        */
+    float horizon;                  /* forecast distance of the output, frames                                          */
+    float img_w, img_h;             /* the stream's camera size: the forecast is clipped to [0, img_w] x [0, img_h]      */
+    float divisor;                  /* det[..., :4] / divisor = camera coordinates                                      */
+    int32_t reserved[3];
+} sy_track_tick;
+typedef struct sy_track_query {     /* 16 bytes of DEVICE memory per forecast entry                                      */
+    int32_t slot;                   /* < 0 or >= n_slots: the entry reports 0 boxes                                      */
+    float horizon, img_w, img_h;
+} sy_track_query;
+typedef struct sy_track_params {    /* HOST memory, copied into the launch: constants of a detector's life              */
+    float match_iou_th;             /* a pair may match from this IoU on                      (reference: 0.3)           */
+    float r, q, p_init;             /* R = r I, Q = dt^2 q I, P of a fresh track = p_init I   (reference: 10, 1, 100)    */
+    int32_t min_size;               /* a forecast box is kept from int(w) * int(h) >= min_size (reference: 75)           */
+    int32_t reserved[3];
+} sy_track_params;
+#define SY_TRACK_MAX_TRACKS 256     /* the compiled maximum of sy_track_state::max_tracks                                */
+typedef struct sy_track_state {     /* HOST memory, copied into the launch; the pools are dense DEVICE tensors, T = max_tracks:
+                                       lane i of the kernel owns track i, so the track index is the fastest one          */
+    float* x;                       /* [n_slots][8][T]   l, t, w, h and their velocities per frame                       */
+    float* P;                       /* [n_slots][36][T]  upper triangle of the 8 x 8 covariance, row-major               */
+    float* score;                   /* [n_slots][T]      obj * class_conf of the detection the track was last built from */
+    int32_t* label;                 /* [n_slots][T]                                                                      */
+    int32_t* id;                    /* [n_slots][T]                                                                      */
+    int32_t* hdr;                   /* [n_slots][4]      n (live tracks), n_matched (the first n_matched tracks were matched
+                                                         at their last rebuild: only they move in a forecast), next_id, 0 */
+    int32_t n_slots, max_tracks;
+} sy_track_state;
+/* sy_track_update, one launch per tick (B workgroups): det [B, max_det, 7] / cnt [B] as sy_postprocess writes them.  Per row
+ * with a slot: reset (row_first), predict by dt_frames, associate, rebuild the slot's track list (matched pairs first, then the
+ * unmatched detections as fresh tracks; unmatched tracks are dropped; cnt == 0 keeps the predicted tracks), store, forecast to
+ * `horizon`: out [B, T, 6] = x1, y1, x2, y2, score, label of the surviving tracks in track order, out_id [B, T], out_cnt [B].
+ * A row without a slot (row_slot < 0 or >= n_slots) writes nothing but out_cnt[b] = 0. */
+SY_API int sy_track_update(const float* det, const int32_t* cnt, int B, int max_det, const int32_t* row_slot,
+                           const uint8_t* row_first, const sy_track_tick* ticks, const sy_track_state* state,
+                           const sy_track_params* params, float* out, int32_t* out_id, int32_t* out_cnt, void* stream);
+/* sy_track_forecast: the forecast step alone for n entries of the DEVICE table `queries` (the state is only read): out
+ * [n, T, 6], out_id [n, T], out_cnt [n] as above. */
+SY_API int sy_track_forecast(const sy_track_query* queries, int n, const sy_track_state* state, const sy_track_params* params,
+                             float* out, int32_t* out_id, int32_t* out_cnt, void* stream);
+
 /* backward of sy_resize_nearest (scatter-add into the source grid) */
 SY_API int sy_resize_nearest_bwd(const void* dout, int N, int Ho, int Wo, int C, int lddo, int64_t dobs,
                           void* din, int Hi, int Wi, int lddi, int64_t dibs, int accumulate,

@@ -13,10 +13,10 @@ from .model.tal_head import TALHead
 from .model.yolox import YOLOX
 from .postprocess import postprocess
 from .data import Surface
-from .streaming import MultiStreamDetector, StreamingDetector
+from .streaming import MultiStreamDetector, StreamingDetector, TrackConfig
 
 __all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model", "DeviceGradScaler",
-           "StreamingDetector", "MultiStreamDetector", "Surface"]
+           "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig"]
 __version__ = "0.1.0"
 
 MODEL_ZOO = {

@@ -104,6 +104,32 @@ class StreamLevel(C.Structure):
                 ("C", C.c_int32), ("ld", C.c_int32)]
 
 
+class TrackTick(C.Structure):
+    """sy_track_tick (include/streamyolo_hip.h): 32 bytes of DEVICE memory per batch row."""
+    _fields_ = [("dt_frames", C.c_int32), ("horizon", C.c_float), ("img_w", C.c_float), ("img_h", C.c_float),
+                ("divisor", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class TrackQuery(C.Structure):
+    """sy_track_query (include/streamyolo_hip.h): 16 bytes of DEVICE memory per forecast entry."""
+    _fields_ = [("slot", C.c_int32), ("horizon", C.c_float), ("img_w", C.c_float), ("img_h", C.c_float)]
+
+
+class TrackParams(C.Structure):
+    """sy_track_params (include/streamyolo_hip.h)."""
+    _fields_ = [("match_iou_th", C.c_float), ("r", C.c_float), ("q", C.c_float), ("p_init", C.c_float),
+                ("min_size", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class TrackState(C.Structure):
+    """sy_track_state (include/streamyolo_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("P", C.c_void_p), ("score", C.c_void_p), ("label", C.c_void_p), ("id", C.c_void_p),
+                ("hdr", C.c_void_p), ("n_slots", C.c_int32), ("max_tracks", C.c_int32)]
+
+
+TRACK_MAX_TRACKS = 256                         # SY_TRACK_MAX_TRACKS
+
+
 def pack_table(rows):
     """ctypes array of PackEntry with the tile0 prefix filled in -> (array, total_tiles)."""
     t = 0
@@ -164,6 +190,8 @@ SIGNATURES = {
     "sy_view_copy": (_I, [_P, _I, _P, _I, _L, _I, _I, _I, _P]),
     "sy_stream_state_gather": (_I, [_P, _I, _L, _P, _I, _P, _I, _L, _I, _I, _I, _I, _P, _P, _I, _P]),
     "sy_stream_state_scatter": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "sy_track_update": (_I, [_P, _P, _I, _I, _P, _P, _P, C.POINTER(TrackState), C.POINTER(TrackParams), _P, _P, _P, _P]),
+    "sy_track_forecast": (_I, [_P, _I, C.POINTER(TrackState), C.POINTER(TrackParams), _P, _P, _P, _P]),
     "sy_splitk_epilogue": (_I, [_P, _I, _L, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "sy_rows_add_f32": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
     "sy_pred_grad_fold_workspace_floats": (_L, [_I]),

@@ -408,6 +408,36 @@ __device__ __forceinline__ unsigned long long sy_readlane64(unsigned long long v
 }
 #endif
 
+// Maximum of x over the 64 lanes of the wave, the same value in every lane (x must not be NaN), and the 32-bit value of lane `l`
+// (wave-uniform l).  Four DPP maxima inside the 16-lane rows (the controls of sy_sum32_upper) and four v_readlane across them:
+// ~30 cycles on the VALU / SALU where six __shfl_xor steps are six ds_bpermute round trips (~100 cycles each) — for serial loops
+// whose every step ends in a reduction (the association of csrc/track.hip).  Every lane of the wave must be active.
+#ifdef SY_EMU
+static inline float sy_wave_max(float x) {
+    for (int off = 1; off < 64; off <<= 1) x = fmaxf(x, __shfl_xor(x, off));
+    return x;
+}
+static inline float sy_readlane(float v, int l) { return __shfl(v, l); }
+static inline int sy_readlane(int v, int l) { return __shfl(v, l); }
+#else
+template <int CTRL>
+__device__ __forceinline__ float sy_max_dpp(float x) {
+    const int moved = __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false);
+    return fmaxf(x, __builtin_bit_cast(float, moved));
+}
+__device__ __forceinline__ int sy_readlane(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float sy_readlane(float v, int l) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+__device__ __forceinline__ float sy_wave_max(float x) {
+    x = sy_max_dpp<0xB1>(x);             // quad_perm [1, 0, 3, 2]
+    x = sy_max_dpp<0x4E>(x);             // quad_perm [2, 3, 0, 1]
+    x = sy_max_dpp<0x141>(x);            // row_half_mirror
+    x = sy_max_dpp<0x140>(x);            // row_mirror: every lane of a 16-lane row holds the row's maximum
+    return fmaxf(fmaxf(sy_readlane(x, 0), sy_readlane(x, 16)), fmaxf(sy_readlane(x, 32), sy_readlane(x, 48)));
+}
+#endif
+
 // ---- write-through 16-byte global store ---------------------------------------------------------------------------------------------
 // A kernel boundary on an in-order stream costs 1.2-1.3 us — unless the finished kernel leaves dirty lines in the eight (mutually
 // non-coherent) L2s: then the end-of-kernel release writes them back first, 2.6-3.2 us from ~17 MB written (tools/probes/

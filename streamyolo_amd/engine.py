@@ -868,6 +868,74 @@ class StreamSlots:
             self._done[self._at] = ev
 
 
+class TrackSlots:
+    """Per-stream tracker state of a batched tick (ops.track_update behind the NMS): the pools of ops.TrackState — slot s = one
+    camera's tracks, the slot numbering of the detector's StreamSlots — the tick's per-row table `ticks` (B sy_track_tick
+    entries: frames since the stream's previous tick, forecast horizon, camera size, box divisor) with a ring of pinned host
+    mirrors and ONE non-blocking upload() (the mechanism of StreamSlots), and the outputs of the launch: out [B, T, 6] (x1, y1,
+    x2, y2, score, label in camera coordinates), out_id [B, T], out_cnt [B].  forecast_* are the same for sy_track_forecast:
+    a query table of up to S entries and its outputs."""
+
+    def __init__(self, plan_or_B, n_slots, max_tracks, device=None):
+        import numpy as np
+        from . import _lib
+        B = plan_or_B if isinstance(plan_or_B, int) else plan_or_B.B
+        device = torch.device(device if device is not None else ("cpu" if isinstance(plan_or_B, int) else plan_or_B.device))
+        self.B, self.S, self.T, self.device = int(B), int(n_slots), int(max_tracks), device
+        self.state = ops.TrackState(self.S, self.T, device)
+        self._tick_dtype, self._query_dtype = np.dtype(_lib.TrackTick), np.dtype(_lib.TrackQuery)
+        assert self._tick_dtype.itemsize == 32 and self._query_dtype.itemsize == 16
+        self.ticks = torch.zeros(32 * self.B, dtype=torch.uint8, device=device)
+        self.out = torch.zeros((self.B, self.T, 6), dtype=torch.float32, device=device)
+        self.out_id = torch.zeros((self.B, self.T), dtype=torch.int32, device=device)
+        self.out_cnt = torch.zeros(self.B, dtype=torch.int32, device=device)
+        cuda = self.ticks.is_cuda
+        self._ring = [torch.zeros(32 * self.B, dtype=torch.uint8) for _ in range(4 if cuda else 1)]
+        if cuda:
+            self._ring = [h.pin_memory() for h in self._ring]
+        self._done = [None] * len(self._ring)
+        self._at = 0
+        self.queries = torch.zeros(16 * self.S, dtype=torch.uint8, device=device)
+        self._queries_host = torch.zeros(16 * self.S, dtype=torch.uint8)
+        if cuda:
+            self._queries_host = self._queries_host.pin_memory()
+        self.forecast_out = torch.zeros((self.S, self.T, 6), dtype=torch.float32, device=device)
+        self.forecast_id = torch.zeros((self.S, self.T), dtype=torch.int32, device=device)
+        self.forecast_cnt = torch.zeros(self.S, dtype=torch.int32, device=device)
+
+    def set_rows(self, rows):
+        """Rows 0..n-1 of the next tick (host side only): (dt_frames, horizon, img_w, img_h, divisor) each; the others zero."""
+        assert len(rows) <= self.B
+        self._at = (self._at + 1) % len(self._ring)
+        if self._done[self._at] is not None:
+            self._done[self._at].synchronize()                       # (only when the device is a whole ring of ticks behind)
+        host = self._ring[self._at]
+        host.zero_()
+        table = host.numpy().view(self._tick_dtype)
+        for b, (dt, horizon, w, h, div) in enumerate(rows):
+            table[b] = (int(dt), float(horizon), float(w), float(h), float(div), (0, 0, 0))
+
+    def upload(self):
+        """The rows of the last set_rows -> the device table: ONE non-blocking copy on the current stream."""
+        self.ticks.copy_(self._ring[self._at], non_blocking=True)
+        if self.ticks.is_cuda:
+            ev = self._done[self._at] or torch.cuda.Event()
+            ev.record()
+            self._done[self._at] = ev
+
+    def forecast(self, entries, params):
+        """sy_track_forecast for entries = [(slot, horizon, img_w, img_h)] (at most S): the first len(entries) rows of
+        forecast_out / forecast_id / forecast_cnt.  The caller reads them back (and so synchronises) before the next call."""
+        n = len(entries)
+        assert 1 <= n <= self.S
+        table = self._queries_host.numpy().view(self._query_dtype)
+        for e, (slot, horizon, w, h) in enumerate(entries):
+            table[e] = (int(slot), float(horizon), float(w), float(h))
+        self.queries.copy_(self._queries_host, non_blocking=True)
+        return ops.track_forecast(self.queries, n, self.state, params, self.forecast_out[:n], self.forecast_id[:n],
+                                  self.forecast_cnt)
+
+
 def _nhwc_of(t, like):
     """NHWC storage of a caller-supplied NCHW-shaped feature tensor, in the plan's dtype."""
     u = t.permute(0, 2, 3, 1)

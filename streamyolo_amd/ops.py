@@ -376,6 +376,75 @@ def stream_state_scatter(curs, pools, row_slot):
           "sy_stream_state_scatter")
 
 
+class TrackState:
+    """The per-slot pools of sy_track_update (sy_track_state of the header): S slots of up to T tracks, the track index fastest
+    (x [S, 8, T], P [S, 36, T]: upper triangles; score / label / id [S, T]; hdr [S, 4] = n, n_matched, next_id, 0), all zero."""
+
+    def __init__(self, n_slots, max_tracks, device):
+        S, T = int(n_slots), int(max_tracks)
+        assert S >= 1 and 1 <= T <= _lib.TRACK_MAX_TRACKS
+        self.S, self.T, self.device = S, T, torch.device(device)
+        self.x = torch.zeros((S, 8, T), dtype=torch.float32, device=device)
+        self.P = torch.zeros((S, 36, T), dtype=torch.float32, device=device)
+        self.score = torch.zeros((S, T), dtype=torch.float32, device=device)
+        self.label = torch.zeros((S, T), dtype=torch.int32, device=device)
+        self.id = torch.zeros((S, T), dtype=torch.int32, device=device)
+        self.hdr = torch.zeros((S, 4), dtype=torch.int32, device=device)
+
+    def tensors(self):
+        return self.x, self.P, self.score, self.label, self.id, self.hdr
+
+    def c_struct(self):
+        s = _lib.TrackState()
+        s.x, s.P, s.score, s.label, s.id, s.hdr = (t.data_ptr() for t in self.tensors())
+        s.n_slots, s.max_tracks = self.S, self.T
+        return s
+
+
+def track_params(match_iou_th=0.3, r=10.0, q=1.0, p_init=100.0, min_size=75):
+    """sy_track_params with the reference's constants as defaults (pps_forecast_kf.py:40, :129-132; extrap_clean_up's min_size)."""
+    p = _lib.TrackParams()
+    p.match_iou_th, p.r, p.q, p.p_init, p.min_size = float(match_iou_th), float(r), float(q), float(p_init), int(min_size)
+    return p
+
+
+def _track_outputs(out, out_id, out_cnt, n, T, device):
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, T, 6) and out.device == device
+    assert out_id.dtype == torch.int32 and out_id.is_contiguous() and tuple(out_id.shape) == (n, T) and out_id.device == device
+    assert out_cnt.dtype == torch.int32 and out_cnt.is_contiguous() and out_cnt.numel() >= n and out_cnt.device == device
+
+
+def track_update(det, cnt, row_slot, row_first, ticks, state, params, out, out_id, out_cnt):
+    """One tick of the tracker behind sy_postprocess (see the header): det [B, max_det, 7] fp32 / cnt int32 [B] as postprocess()
+    returns them; row_slot int32 [B], row_first uint8 [B] (engine.StreamSlots) and ticks uint8 [B * 32] (B sy_track_tick
+    entries; engine.TrackSlots): device tables, read by the kernel at run time; state: TrackState; params: track_params().
+    Writes out [B, T, 6] (x1, y1, x2, y2, score, label), out_id int32 [B, T], out_cnt int32 [B]; returns them."""
+    assert det.dtype == torch.float32 and det.is_contiguous() and det.dim() == 3 and det.shape[2] == 7
+    B, max_det = det.shape[:2]
+    dev = state.device
+    assert det.device == dev and cnt.dtype == torch.int32 and cnt.is_contiguous() and cnt.numel() >= B and cnt.device == dev
+    _stream_tables(row_slot, row_first, B, dev)
+    assert ticks.dtype == torch.uint8 and ticks.is_contiguous() and ticks.numel() >= 32 * B and ticks.device == dev
+    _track_outputs(out, out_id, out_cnt, B, state.T, dev)
+    st = state.c_struct()
+    check(_lib.lib().sy_track_update(det.data_ptr(), cnt.data_ptr(), B, max_det, row_slot.data_ptr(), row_first.data_ptr(),
+                                     ticks.data_ptr(), C.byref(st), C.byref(params), out.data_ptr(), out_id.data_ptr(),
+                                     out_cnt.data_ptr(), stream_of(det)), "sy_track_update")
+    return out, out_id, out_cnt
+
+
+def track_forecast(queries, n, state, params, out, out_id, out_cnt):
+    """The forecast step alone for the first n sy_track_query entries (slot, horizon, img_w, img_h) of the device table
+    `queries` (uint8 [>= n * 16]); the state is only read.  Writes and returns out [n, T, 6], out_id [n, T], out_cnt [n]."""
+    dev = state.device
+    assert queries.dtype == torch.uint8 and queries.is_contiguous() and queries.numel() >= 16 * n and queries.device == dev
+    _track_outputs(out, out_id, out_cnt, n, state.T, dev)
+    st = state.c_struct()
+    check(_lib.lib().sy_track_forecast(queries.data_ptr(), n, C.byref(st), C.byref(params), out.data_ptr(), out_id.data_ptr(),
+                                       out_cnt.data_ptr(), stream_of(out)), "sy_track_forecast")
+    return out, out_id, out_cnt
+
+
 def rows_add_f32(dst, src, rows, cols, ldd, lds, zero_src=False):
     """dst[r][:cols] += src[r][:cols] (fp32, row pitches ldd / lds in elements); zero_src: clear the source behind the read."""
     assert dst.dtype == torch.float32 and src.dtype == torch.float32

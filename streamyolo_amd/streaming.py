@@ -61,6 +61,26 @@ def _parse(det, cnt, in_scale):
     return d[:, :4] / in_scale, d[:, 4] * d[:, 5], d[:, 6].astype(np.int32), None
 
 
+class TrackConfig:
+    """Options of the device tracker behind the NMS (MultiStreamDetector(track=...); csrc/track.hip).  The defaults are the
+    reference's constants: match_iou_th (pps_forecast_kf.py:40), r / q / p_init = the diagonals of kf_R, kf_Q and kf_P_init
+    (:129-132), min_size (extrap_clean_up, sAP/forecast/__init__.py:33).  max_tracks: tracks kept per stream, at most 256; a
+    frame's detections beyond it (the lowest scores) are dropped by the tracker."""
+
+    def __init__(self, match_iou_th=0.3, r=10.0, q=1.0, p_init=100.0, min_size=75, max_tracks=256):
+        from ._lib import TRACK_MAX_TRACKS
+        if not 1 <= int(max_tracks) <= TRACK_MAX_TRACKS:
+            raise ValueError("TrackConfig: max_tracks must be in 1..%d, got %r" % (TRACK_MAX_TRACKS, max_tracks))
+        if not float(match_iou_th) > 0.0:
+            raise ValueError("TrackConfig: match_iou_th must be positive, got %r" % (match_iou_th,))
+        self.match_iou_th, self.r, self.q, self.p_init = float(match_iou_th), float(r), float(q), float(p_init)
+        self.min_size, self.max_tracks = int(min_size), int(max_tracks)
+
+    def __repr__(self):
+        return "TrackConfig(match_iou_th=%r, r=%r, q=%r, p_init=%r, min_size=%r, max_tracks=%r)" % (
+            self.match_iou_th, self.r, self.q, self.p_init, self.min_size, self.max_tracks)
+
+
 class StreamingDetector:
     """The model-side state of streamyolo_det.py's loop: `model.eval().half()` (:104-109), ten warm-up calls (:113-120),
     then per camera frame `preproc` -> `model(frame, buffer=buffer, mode='on_pipe')` -> `inference` (:176-181), the
@@ -175,10 +195,23 @@ class MultiStreamDetector:
         cam = det.open(pixel_format="nv12")
         det([Surface.from_buffer(decoded, 1080, 1920, "nv12", chroma_row=1088)], [cam])
 
+    track=TrackConfig() (or True for its defaults) adds the reference's streaming post-processing step (pps_forecast_kf.py with
+    --forecast-before-assoc) on the device: per stream, a Kalman filter per track, greedy IoU association of each frame's
+    detections with the predicted tracks, and the boxes forecast `horizon` frames ahead, clipped to the stream's camera — one
+    more launch on the same tape (sy_track_update), state in one more per-slot pool (engine.TrackSlots).  Calls then take
+    frame_idx (one int per frame; default: the stream's previous index + 1; the filter's dt is the difference to the previous
+    index, which must be >= 1 except at a sequence start) and horizon (a float or one per frame, default 0), results are
+    5-tuples (bboxes, scores, labels, None, track_ids) — the forecast boxes in camera coordinates — and forecast(sids, horizon)
+    moves the current tracks to another time without a frame.
+
+        det = MultiStreamDetector(model, (1200, 1920), batch=8, track=True); det.warm_up()
+        cam = det.open()
+        (boxes, scores, labels, _, ids), = det([frame], [cam], frame_idx=[12], horizon=1.0)
+
     Which frames go into a tick is the caller's scheduling policy."""
 
     def __init__(self, model, frame_hw, max_streams=16, batch=8, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65,
-                 dtype="fp16", device="cuda", max_frame_hw=None, pixel_format="bgr", surfaces=False):
+                 dtype="fp16", device="cuda", max_frame_hw=None, pixel_format="bgr", surfaces=False, track=None):
         self.pixel_format, self.surfaces = pixel_format, bool(surfaces)
         self._frame_shape = _stream_shape(frame_hw, pixel_format, self.surfaces)     # (ValueError before anything is built)
         if int(batch) < 1 or int(max_streams) < 1:
@@ -221,6 +254,21 @@ class MultiStreamDetector:
         self.state = StreamSlots(self.plan, self.max_streams)
         self._ws = ops.PostprocessWorkspace(self.batch, self.plan.A, self.device)          # its own: results live until the next tick
         self._post = lambda out: ops.postprocess(out, num_classes, conf_thre, nms_thresh, self._ws)   # one object: part of the tape key
+        self.track = TrackConfig() if track is True else (track or None)
+        self.tracks = None
+        if self.track is not None:
+            from .engine import TrackSlots
+            cfg = self.track
+            self.tracks = TrackSlots(self.plan, self.max_streams, cfg.max_tracks)
+            self._track_prm = ops.track_params(cfg.match_iou_th, cfg.r, cfg.q, cfg.p_init, cfg.min_size)
+
+            def post(out):                                       # the NMS, then the tracker on its output: one more launch
+                det, index, cnt = ops.postprocess(out, num_classes, conf_thre, nms_thresh, self._ws)
+                ops.track_update(det, cnt, self.state.row_slot, self.state.row_first, self.tracks.ticks, self.tracks.state,
+                                 self._track_prm, self.tracks.out, self.tracks.out_id, self.tracks.out_cnt)
+                return det, index, cnt
+            self._post = post
+        self._fidx = {}                                          # open stream id -> frame index of its previous frame (tracking)
         self._slot_of = {}                                       # open stream id -> pool slot
         self._first = {}                                         # open stream id -> its next frame starts a sequence
         self._free = list(range(self.max_streams))
@@ -255,6 +303,7 @@ class MultiStreamDetector:
         self._first[sid] = True
         self._geom[sid] = geom
         self._fmt[sid] = (pixel_format, shape)
+        self._fidx[sid] = None
         return sid
 
     def _known(self, sid):
@@ -274,6 +323,7 @@ class MultiStreamDetector:
         del self._first[sid]
         del self._geom[sid]
         del self._fmt[sid]
+        del self._fidx[sid]
 
     def warm_up(self, n=10):
         """streamyolo_det.py:113-120 on a dummy batch (no row carries a frame: no stream's state is written); builds, tunes and
@@ -286,6 +336,9 @@ class MultiStreamDetector:
             self._in.upload()
         self.state.set_rows((), ())
         self.state.upload()
+        if self.tracks is not None:
+            self.tracks.set_rows(())
+            self.tracks.upload()
         with torch.no_grad():
             for _ in range(max(int(n), 2)):                      # (a tuning + recording tick, then at least one replay)
                 self.plan.run_stream_slots_taped(self._in, self.state, post=self._post)
@@ -324,7 +377,33 @@ class MultiStreamDetector:
             fs.append(f)
         return fs
 
-    def _tick(self, frames, sids):
+    def _check_times(self, sids, frame_idx, horizon):
+        """Per frame (frame index, dt, horizon) of a call with tracking — found wrong BEFORE anything is written: ValueError."""
+        n = len(sids)
+        if self.tracks is None:
+            if frame_idx is not None or horizon is not None:
+                raise ValueError("MultiStreamDetector: frame_idx / horizon need a detector built with track=...")
+            return [None] * n
+        if frame_idx is not None and len(frame_idx) != n:
+            raise ValueError("MultiStreamDetector: %d frame indices for %d frames" % (len(frame_idx), n))
+        if horizon is None:
+            horizon = 0.0
+        hs = [float(horizon)] * n if np.isscalar(horizon) else [float(h) for h in horizon]
+        if len(hs) != n:
+            raise ValueError("MultiStreamDetector: %d horizons for %d frames" % (len(hs), n))
+        prev, first, out = dict(self._fidx), dict(self._first), []
+        for k, sid in enumerate(sids):
+            start = first[sid] or prev[sid] is None
+            idx = int(frame_idx[k]) if frame_idx is not None else (0 if prev[sid] is None else prev[sid] + 1)
+            dt = 0 if start else idx - prev[sid]
+            if not start and dt < 1:
+                raise ValueError("MultiStreamDetector: frame index %d of stream %r does not follow its previous frame %d"
+                                 % (idx, sid, prev[sid]))
+            prev[sid], first[sid] = idx, False
+            out.append((idx, dt, hs[k]))
+        return out
+
+    def _tick(self, frames, sids, times=None):
         n = len(sids)
         if self._stage is not None:
             for b, f in enumerate(frames):
@@ -339,32 +418,77 @@ class MultiStreamDetector:
             self._in.upload()
         self.state.set_rows([self._slot_of[s] for s in sids], [self._first[s] for s in sids])
         self.state.upload()
+        if self.tracks is not None:
+            rows = []
+            for s, (idx, dt, horizon) in zip(sids, times):
+                (h, w), _, div = self._geom[s]
+                rows.append((dt, horizon, w, h, div))
+                self._fidx[s] = idx
+            self.tracks.set_rows(rows)
+            self.tracks.upload()
         for s in sids:
             self._first[s] = False
         with torch.no_grad():
             det, _, cnt = self.plan.run_stream_slots_taped(self._in, self.state, post=self._post)
         return det, cnt, n
 
-    def detect_device(self, frames, sids):
+    def detect_device(self, frames, sids, frame_idx=None, horizon=None):
         """One tick (len(frames) <= batch) without any host read: (det [batch, A, 7], cnt [batch], rows) — rows 0..rows-1 of
         the device tensors belong to `sids` in order (kept detections det[b, :cnt[b]]: x1, y1, x2, y2 on the network input,
         obj, class_conf, class), the other rows are meaningless.  The tensors are detector-owned and overwritten by the next
         tick.  Frames are copied into the staging tensor, the tables go up in one non-blocking copy from pinned memory.
         Mixed mode returns a fourth value: the device tensor div [batch] (float32, detector-owned) — the boxes of row b divided
-        by div[b] are in that stream's camera coordinates (what __call__ does on the host)."""
+        by div[b] are in that stream's camera coordinates (what __call__ does on the host).
+        With tracking, three more values follow: the tracker's device tensors out [batch, max_tracks, 6] (x1, y1, x2, y2, score,
+        label of the forecast tracks, camera coordinates), out_id [batch, max_tracks] and out_cnt [batch] (engine.TrackSlots)."""
         if len(sids) > self.batch:
             raise ValueError("MultiStreamDetector: %d frames in one tick of batch %d" % (len(sids), self.batch))
-        res = self._tick(self._check(frames, sids), list(sids))
-        return res if self._stage is not None else res + (self._in.divisor,)
+        fs, sids = self._check(frames, sids), list(sids)
+        res = self._tick(fs, sids, self._check_times(sids, frame_idx, horizon))
+        if self._stage is None:
+            res = res + (self._in.divisor,)
+        return res if self.tracks is None else res + (self.tracks.out, self.tracks.out_id, self.tracks.out_cnt)
 
-    def __call__(self, frames, sids):
+    def _parse_tracks(self, out, out_id, out_cnt, n):
+        """Rows 0..n-1 of a tracker output -> (bboxes, scores, labels, None, track_ids) host tuples (one copy each: synchronises)."""
+        counts = out_cnt[:n].cpu().numpy()
+        top = max(int(counts.max()), 1)
+        rows, ids = out[:n, :top].cpu().numpy(), out_id[:n, :top].cpu().numpy()
+        return [(rows[b, :c, :4], rows[b, :c, 4], rows[b, :c, 5].astype(np.int32), None, ids[b, :c])
+                for b, c in ((b, int(counts[b])) for b in range(n))]
+
+    def forecast(self, sids, horizon=0.0):
+        """The current tracks of the streams `sids` moved `horizon` frames (a float or one per stream) past their last frame,
+        without a tick: (bboxes, scores, labels, None, track_ids) per stream, as __call__ returns them (sy_track_forecast; the
+        tracker's state is only read).  What the reference does for every output frame between two detections."""
+        if self.tracks is None:
+            raise ValueError("MultiStreamDetector: forecast() needs a detector built with track=...")
+        sids = list(sids)
+        for sid in sids:
+            self._known(sid)
+        hs = [float(horizon)] * len(sids) if np.isscalar(horizon) else [float(h) for h in horizon]
+        if len(hs) != len(sids):
+            raise ValueError("MultiStreamDetector: %d horizons for %d streams" % (len(hs), len(sids)))
+        res = []
+        for t0 in range(0, len(sids), self.max_streams):
+            part = sids[t0:t0 + self.max_streams]
+            entries = [(self._slot_of[s], h, self._geom[s][0][1], self._geom[s][0][0]) for s, h in zip(part, hs[t0:])]
+            res += self._parse_tracks(*self.tracks.forecast(entries, self._track_prm), len(part))
+        return res
+
+    def __call__(self, frames, sids, frame_idx=None, horizon=None):
         """n camera frames (uint8 [H, W, 3] arrays or tensors; surfaces=True: data.Surface too) and the ids of their streams -> n (bboxes, scores, labels, None)
         host tuples in the order given, each what StreamingDetector returns for that frame.  n > batch: consecutive ticks.
-        Every tick ends with the device synchronised by the copy of its counts and kept rows."""
+        Every tick ends with the device synchronised by the copy of its counts and kept rows.
+        With tracking: 5-tuples (bboxes, scores, labels, None, track_ids) of the tracker's forecast output (see the class)."""
         fs, sids = self._check(frames, sids), list(sids)
+        times = self._check_times(sids, frame_idx, horizon)
         res = []
         for t0 in range(0, len(sids), self.batch):
-            det, cnt, n = self._tick(fs[t0:t0 + self.batch], sids[t0:t0 + self.batch])
+            det, cnt, n = self._tick(fs[t0:t0 + self.batch], sids[t0:t0 + self.batch], times[t0:t0 + self.batch])
+            if self.tracks is not None:
+                res += self._parse_tracks(self.tracks.out, self.tracks.out_id, self.tracks.out_cnt, n)
+                continue
             counts = cnt[:n].cpu().numpy()
             rows = det[:n, :max(int(counts.max()), 1)].cpu().numpy()
             for b in range(n):

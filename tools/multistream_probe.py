@@ -31,6 +31,18 @@ MultiStreamDetector(surfaces=True) with every row a data.Surface read where it l
 the second detector out (the same measurement on a tree that has no surfaces).
 
     python tools/multistream_probe.py --surfaces 1 --pixel-format nv12 --batches 1,8
+
+--track 1: the tick of MultiStreamDetector(track=True) — the tracker launch (sy_track_update) behind the NMS on the same tape —
+beside the untracked tick at the same batch (two detectors over two copies of the model), in one process, alternating: `untracked_ms_per_tick`, `tracked_ms_per_tick`, the
+per-round times of both, `tracked_minus_untracked_ms` (best round minus best round; to be read against the spread) and the mean
+detections per row the tracker saw.  Every row also carries `track_kernel_us`: sy_track_update alone at this batch on synthetic
+rows of 30 and of 256 persisting detections (every detection matches its track: the whole serial association loop runs),
+--ticks launches replayed back to back from a launch tape between two events (the launch gaps included).  --untracked-only 1 leaves the tracked detector out, and
+--tree PATH imports the package of another checkout of the repository (its own library): together the same measurement on
+a tree that has no tracker.
+
+    python tools/multistream_probe.py --track 1 --batches 1,8
+    python tools/multistream_probe.py --track 1 --untracked-only 1 --tree _base --batches 1,8
 """
 import argparse
 import json
@@ -39,6 +51,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv[1:-1]:                                   # (before anything of the package is imported)
+    ROOT = os.path.abspath(sys.argv[sys.argv.index("--tree") + 1])
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
@@ -62,6 +76,9 @@ def main():
     ap.add_argument("--surfaces", type=int, default=0,
                     help="1: the mixed-mode tick of --pixel-format cameras, staged beside every row a Surface read in place")
     ap.add_argument("--staged-only", type=int, default=0, help="with --surfaces 1: only the staged tick (runs on older trees)")
+    ap.add_argument("--track", type=int, default=0, help="1: the tracked tick beside the untracked tick of the same batch")
+    ap.add_argument("--untracked-only", type=int, default=0, help="with --track 1: only the untracked tick (runs on older trees)")
+    ap.add_argument("--tree", default=None, help="root of another checkout of the repository to import the package from")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -180,6 +197,74 @@ def main():
             del ticks, staged
             if not args.staged_only:
                 del inplace, surfs
+        print(emit())
+        return
+
+    if args.track:
+        if args.mixed or args.surfaces or fmt != "bgr":
+            ap.error("--track is a separate measurement")
+        from streamyolo_amd.streaming import MultiStreamDetector
+        res.update({"track": True, "tree": ROOT})
+        for B in batches:
+            kw = dict(max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+            plain = MultiStreamDetector(model, hw, **kw)
+            plain.warm_up(args.warmup)
+            p_sids = [plain.open() for _ in range(B)]
+            ticks = {"untracked": lambda: plain.detect_device(frames[:B], p_sids)}
+            row = {"batch": B, "active": B}
+            if not args.untracked_only:
+                twin = sy.build_model(args.model)                # (its own plan: no tape is re-recorded when the ticks alternate)
+                twin.load_state_dict(model.state_dict(), strict=True)
+                tracked = MultiStreamDetector(twin, hw, track=True, **kw)
+                tracked.warm_up(args.warmup)
+                t_sids = [tracked.open() for _ in range(B)]
+                ticks["tracked"] = lambda: tracked.detect_device(frames[:B], t_sids)
+            rounds = {k: [] for k in ticks}
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                for k, fn in ticks.items():
+                    fn()                                         # (untimed: first rows done; a tape re-recorded after a switch)
+                    rounds[k].append(timed(fn, args.ticks)[0])
+            for k, v in rounds.items():
+                row.update({k + "_ms_per_tick": min(v), k + "_ms_rounds": v, k + "_spread_ms": max(v) - min(v)})
+            if "tracked" in rounds:
+                from streamyolo_amd import ops
+                row["tracked_minus_untracked_ms"] = min(rounds["tracked"]) - min(rounds["untracked"])
+                r = tracked.detect_device(frames[:B], t_sids)    # (one more tick: what the tracker had to do)
+                row["detections_per_row"] = r[1][:B].cpu().tolist()
+                row["tracks_out_per_row"] = r[-1][:B].cpu().tolist()
+                row["tracks_matched_per_row"] = tracked.tracks.state.hdr[:, 1].cpu().tolist()
+                # the kernel alone: rows of k boxes on a grid that come back every tick
+                ts, T, us = tracked.tracks, tracked.tracks.T, {}
+                for k in (30, T):
+                    g = torch.arange(k, device=dev, dtype=torch.float32)
+                    box = torch.stack([(g % 32) * 40, (g // 32) * 40, (g % 32) * 40 + 32, (g // 32) * 40 + 32,
+                                       1.0 - g / (2 * T), torch.ones_like(g), g % 8], dim=1)
+                    det_k = torch.zeros((B, T, 7), device=dev)
+                    det_k[:, :k] = box
+                    cnt_k = torch.full((B,), k, dtype=torch.int32, device=dev)
+                    ts.set_rows([(1, 0.0, float(hw[1]), float(hw[0]), 0.5)] * B)
+                    ts.upload()
+                    slot = torch.arange(B, dtype=torch.int32, device=dev)
+                    first = torch.zeros(B, dtype=torch.uint8, device=dev)
+
+                    def kernel():
+                        ops.track_update(det_k, cnt_k, slot, first, ts.ticks, ts.state, tracked._track_prm, ts.out, ts.out_id, ts.out_cnt)
+                    ops.track_update(det_k, cnt_k, slot, first.fill_(1), ts.ticks, ts.state, tracked._track_prm, ts.out, ts.out_id, ts.out_cnt)
+                    first.zero_()
+                    kernel()
+                    tape = _lib.NativeTape()                     # (the launches re-issued from C: the Python wrapper costs more than
+                    with tape:                                   #  the kernel takes at 30 detections)
+                        for _ in range(args.ticks):
+                            kernel()
+                    stream = ops.stream_of(det_k)
+                    tape.replay(stream, None)
+                    us[str(k)] = 1e3 * min(timed(lambda: tape.replay(stream, None), 3)[0] for _ in range(args.rounds)) / args.ticks
+                    assert int(ts.state.hdr[:B, 1].min()) == k   # every detection matched its track
+                row["track_kernel_us"] = us
+                del tracked, twin
+            res["rows"].append(row)
+            emit()
+            del ticks, plain
         print(emit())
         return
 
