@@ -1,6 +1,8 @@
 """sy_tal_loss (SimOTA + Trend-Aware loss + gradient) vs the oracle restatement of the reference's
 TALHead.get_losses, on the golden raw head outputs whose assignment was captured from the
-reference's own get_assignments (tests/golden/nano_simota_2x96x160.npz)."""
+reference's own get_assignments (tests/golden/nano_simota_2x96x160.npz).
+In the golden and in the random inputs below the predicted boxes barely overlap their ground truths: dynamic k is 1 for every
+ground truth here (the golden does hold conflicts).  k > 1 and full top-ten lists are tests/test_kernels_loss_simota.py."""
 import os
 
 import numpy as np
