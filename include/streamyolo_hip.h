@@ -435,6 +435,21 @@ SY_API int sy_bn_silu_bwd_apply(const void* y, int ldy, const void* da, int ldda
                                 const float* gamma, const float* sums, int copies, void* dy, int lddy,
                                 int64_t pixels, int C, float* dgamma, float* dbeta, void* dres, int lddres,
                                 int dres_accumulate, int dtype, int nseg, void* stream);
+/* LIVE ROWS of the backward sums.  The exact mode sizes `sums` for the reduce cap (768 rows per segment); one reduce launch
+ * writes only the rows its own workgroups map to — the prefix [0, min(grid.x, copies)) of each segment — and leaves the rest
+ * +0.0f.  The library reports grid.x from the launch's own geometry and the apply pass folds only those rows: the same additions
+ * in the same order as the fold over all rows (x + 0.0f == x), so every bit of the result is unchanged.
+ * Added to ABI 7 (nothing existing changed).
+ * sy_bn_bwd_reduce_live_rows: *rows = grid.x of sy_bn_silu_bwd_reduce(pixels, C, dtype, nseg) under the cap in force NOW
+ *   (sy_bn_grid_caps); no stream, nothing is launched.  The caller takes min(rows, copies).
+ * sy_bn_silu_bwd_apply_live: sy_bn_silu_bwd_apply whose replica fold stops at row `live` (1 <= live <= copies; one live row
+ *   needs no fold launch; 0 = all rows through the original fold). */
+SY_API int sy_bn_bwd_reduce_live_rows(int64_t pixels, int C, int dtype, int nseg, int32_t* rows);
+SY_API int sy_bn_silu_bwd_apply_live(const void* y, int ldy, const void* da, int ldda, const float* scale,
+                                     const float* shift, const float* mean, const float* invstd,
+                                     const float* gamma, const float* sums, int copies, int live, void* dy, int lddy,
+                                     int64_t pixels, int C, float* dgamma, float* dbeta, void* dres, int lddres,
+                                     int dres_accumulate, int dtype, int nseg, void* stream);
 
 /* SimOTA assignment + Trend-Aware loss, forward and gradient, for a whole batch, no host sync.
  * raw [B, A, 5+nc] fp32 raw head logits (reg4, obj, cls); labels/support [B, max_labels, 5] fp32 rows

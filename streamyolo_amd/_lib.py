@@ -179,6 +179,8 @@ SIGNATURES = {
     "sy_bn_finalize": (_I, [_P, _P, _I, _I, _D, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I, _P]),
     "sy_bn_silu_apply": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _L, _I, _I, _I, _P]),
     "sy_bn_finalize_apply": (_I, [_P, _P, _I, _D, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _L, _I, _I, _I, _P]),
+    "sy_bn_bwd_reduce_live_rows": (_I, [_L, _I, _I, _I, C.POINTER(C.c_int32)]),
+    "sy_bn_silu_bwd_apply_live": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _L, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sy_bn_silu_bwd_reduce": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P]),
     "sy_bn_silu_bwd_apply": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _L, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sy_tal_loss_workspace_bytes": (_L, [_I, _I, _I]),
@@ -259,7 +261,7 @@ class _TapeProxy:
     def __getattr__(self, name):
         fn = getattr(self.real, name)
         tape = self.tape
-        if name.endswith("_supported") or name.endswith("_bytes") or name.endswith("_floats") or name.endswith("version") or name.endswith("_caps") or name.startswith("sy_tape_"):
+        if name.endswith("_supported") or name.endswith("_bytes") or name.endswith("_floats") or name.endswith("version") or name.endswith("_caps") or name.endswith("_live_rows") or name.startswith("sy_tape_"):
             return fn                                           # queries: no stream argument, nothing to replay
 
         def call(*args):

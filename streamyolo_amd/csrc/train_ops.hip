@@ -765,6 +765,47 @@ __global__ __launch_bounds__(kBlock) void fold_replicas_kernel(float* sums, int 
     if (q == 0 && i < n) sums[i] = ((part[0][el] + part[1][el]) + part[2][el]) + part[3][el];
 }
 
+// ---- the same fold over the LIVE rows only -------------------------------------------------------------------------------------
+// A reduce launch writes only the first `live` = min(grid.x, copies) rows of a segment (sy_bn_bwd_reduce_live_rows); the rows
+// are sized for the reduce cap (768) and the rest stays +0.0f.  x + (+0.0f) == x for every x, and a live row is never -0.0f (it is
+// +0 + a from the atomic), so stopping a chain at its last live row leaves every bit of the result as fold_replicas_kernel
+// computes it.  A chain = the elements p[0], p[pitch], p[2 pitch], ... (n of them) added in index order onto +0.0f.  Sixteen
+// loads are issued before the sixteen dependent adds (fold_replicas_kernel waits for four at a time: one memory round trip per
+// four rows, 48 of them in a row at 768 rows and 2C / 64 workgroups).
+__device__ __forceinline__ float fold_chain(const float* p, long long pitch, int n) {
+    float acc = 0.0f;
+    int k = 0;
+    for (; k + 16 <= n; k += 16) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = p[(long long)(k + u) * pitch];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc += v[u];
+    }
+    if (k < n) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = (k + u < n) ? p[(long long)(k + u) * pitch] : 0.0f;
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+            if (k + u < n) acc += v[u];
+    }
+    return acc;
+}
+
+// fold_replicas_kernel over rows [0, live) of segments `copies` rows apart (same grid, same tree: see fold_chain)
+__global__ __launch_bounds__(kBlock) void fold_replicas_live_kernel(float* sums, int n, int copies, int live) {
+    __shared__ float part[4][64];
+    const int el = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int i = blockIdx.x * 64 + el;
+    sums += (long long)blockIdx.y * copies * n;
+    float a = 0.0f;
+    if (i < n) a = fold_chain(sums + (long long)q * n + i, (long long)4 * n, live > q ? (live - q + 3) / 4 : 0);
+    part[q][el] = a;
+    __syncthreads();
+    if (q == 0 && i < n) sums[i] = ((part[0][el] + part[1][el]) + part[2][el]) + part[3][el];
+}
+
 inline bool chunk_rows_ok(int C, int e) { const int cpp = C / e; return cpp >= 1 && cpp <= kBlock; }
 
 inline int env_cap(const char* name, int dflt) {          // tuning knob (tools/): workgroups per launch of the row kernels
@@ -909,13 +950,8 @@ extern "C" int sy_bn_finalize_apply(const float* sum, const float* sqsum, int co
                                        (typename T::elem*)out, ldo, (long long)pixels, C, CS));
 }
 
-extern "C" int sy_bn_silu_bwd_reduce(const void* y, int ldy, const void* da, int ldda, const float* scale,
-                                     const float* shift, const float* mean, const float* invstd, float* sums,
-                                     int copies, int64_t pixels, int C, int dtype, int nseg, void* stream) {
-    if (y == nullptr || da == nullptr || sums == nullptr || pixels <= 0 || C <= 0 || copies <= 0 || nseg < 1) return SY_ERR_ARG;
-    const int e = epc_of(dtype);
-    if (C % e || ldy % e || ldda % e) return SY_ERR_UNSUPPORTED;
-    if (!chunk_rows_ok(C, e)) return SY_ERR_UNSUPPORTED;
+// grid.x of the backward reduce under the cap in force (launch and sy_bn_bwd_reduce_live_rows share it); *CS = its channel slice
+static int reduce_grid_x(long long pixels, int C, int e, int nseg, int* CS_out) {
     const int cap_reduce = bn_cap(kCapReduce).load(std::memory_order_relaxed);
     static const int slice_max = env_cap("SY_BN_REDUCE_SLICE", 64);
     // channel slice of a workgroup: the largest chunk multiple <= 64 channels that divides C (64 = one 128-byte line per row)
@@ -925,7 +961,33 @@ extern "C" int sy_bn_silu_bwd_reduce(const void* y, int ldy, const void* da, int
     const int nsl = C / CS;
     int cap = cap_reduce / (nseg * nsl);
     if (cap < 1) cap = 1;
-    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((bn_silu_bwd_reduce_kernel<T>), dim3(row_grid(pixels, CS, e, cap), nseg, nsl), dim3(kBlock), 0, stream,
+    *CS_out = CS;
+    return row_grid(pixels, CS, e, cap);
+}
+
+// The reduce's workgroup blockIdx.x adds into row blockIdx.x % copies of its segment: rows at or above min(grid.x, copies) stay
+// untouched.  *rows = grid.x of a sy_bn_silu_bwd_reduce launch with these arguments NOW (the cap is process-wide and may be set
+// later: ask when the launch is issued or recorded, not when buffers are sized).
+extern "C" int sy_bn_bwd_reduce_live_rows(int64_t pixels, int C, int dtype, int nseg, int32_t* rows) {
+    if (rows == nullptr || pixels <= 0 || C <= 0 || nseg < 1 || dtype < SY_DT_BF16 || dtype > SY_DT_F32) return SY_ERR_ARG;
+    const int e = epc_of(dtype);
+    if (C % e || !chunk_rows_ok(C, e)) return SY_ERR_UNSUPPORTED;
+    int CS;
+    *rows = reduce_grid_x(pixels, C, e, nseg, &CS);
+    return SY_OK;
+}
+
+extern "C" int sy_bn_silu_bwd_reduce(const void* y, int ldy, const void* da, int ldda, const float* scale,
+                                     const float* shift, const float* mean, const float* invstd, float* sums,
+                                     int copies, int64_t pixels, int C, int dtype, int nseg, void* stream) {
+    if (y == nullptr || da == nullptr || sums == nullptr || pixels <= 0 || C <= 0 || copies <= 0 || nseg < 1) return SY_ERR_ARG;
+    const int e = epc_of(dtype);
+    if (C % e || ldy % e || ldda % e) return SY_ERR_UNSUPPORTED;
+    if (!chunk_rows_ok(C, e)) return SY_ERR_UNSUPPORTED;
+    int CS;
+    const int gx = reduce_grid_x(pixels, C, e, nseg, &CS);
+    const int nsl = C / CS;
+    SY_DISPATCH_DTYPE(dtype, SY_LAUNCH((bn_silu_bwd_reduce_kernel<T>), dim3(gx, nseg, nsl), dim3(kBlock), 0, stream,
                                        (const typename T::elem*)y, ldy, (const typename T::elem*)da, ldda, scale, shift,
                                        mean, invstd, sums, (long long)pixels, C, CS, copies));
 }
@@ -935,7 +997,19 @@ extern "C" int sy_bn_silu_bwd_apply(const void* y, int ldy, const void* da, int 
                                     const float* sums, int copies, void* dy, int lddy, int64_t pixels, int C,
                                     float* dgamma, float* dbeta, void* dres, int lddres, int dres_accumulate, int dtype,
                                     int nseg, void* stream) {
-    if (y == nullptr || da == nullptr || sums == nullptr || dy == nullptr || pixels <= 0 || C <= 0 || copies <= 0 || nseg < 1)
+    return sy_bn_silu_bwd_apply_live(y, ldy, da, ldda, scale, shift, mean, invstd, gamma, sums, copies, 0, dy, lddy, pixels, C, dgamma,
+                                     dbeta, dres, lddres, dres_accumulate, dtype, nseg, stream);
+}
+
+// live > 0: only rows [0, live) of each segment's `copies` were written since the clear (sy_bn_bwd_reduce_live_rows): the fold
+// stops there (fold_replicas_live_kernel; one live row needs no fold launch at all).  live == 0: sy_bn_silu_bwd_apply.
+extern "C" int sy_bn_silu_bwd_apply_live(const void* y, int ldy, const void* da, int ldda, const float* scale,
+                                         const float* shift, const float* mean, const float* invstd, const float* gamma,
+                                         const float* sums, int copies, int live, void* dy, int lddy, int64_t pixels, int C,
+                                         float* dgamma, float* dbeta, void* dres, int lddres, int dres_accumulate, int dtype,
+                                         int nseg, void* stream) {
+    if (y == nullptr || da == nullptr || sums == nullptr || dy == nullptr || pixels <= 0 || C <= 0 || copies <= 0 || nseg < 1 ||
+        live < 0 || live > copies)
         return SY_ERR_ARG;
     const long long seg_sum_stride = (long long)copies * 2 * C;
     if ((dgamma == nullptr) != (dbeta == nullptr)) return SY_ERR_ARG;
@@ -944,8 +1018,13 @@ extern "C" int sy_bn_silu_bwd_apply(const void* y, int ldy, const void* da, int 
     if (!chunk_rows_ok(C, e) || C > 1024) return SY_ERR_UNSUPPORTED;
     static const int fold_inline = env_cap("SY_BN_FOLD_INLINE", 2);      // replicas <= this: every workgroup folds them itself
     if (copies > fold_inline) {       // many replicas: fold once here instead of in every workgroup of the apply pass
-        SY_LAUNCH(fold_replicas_kernel, dim3((2 * C + 63) / 64, nseg), dim3(kBlock), 0, stream,
-                  const_cast<float*>(sums), 2 * C, copies);
+        if (live == 0) {
+            SY_LAUNCH(fold_replicas_kernel, dim3((2 * C + 63) / 64, nseg), dim3(kBlock), 0, stream,
+                      const_cast<float*>(sums), 2 * C, copies);
+        } else if (live > 1) {
+            SY_LAUNCH(fold_replicas_live_kernel, dim3((2 * C + 63) / 64, nseg), dim3(kBlock), 0, stream,
+                      const_cast<float*>(sums), 2 * C, copies, live);
+        }
         copies = 1;
     }
     // (grid caps re-swept after the instruction diet of these kernels, profiles/r02/ai_*, aj_*: fewer, fatter workgroups —

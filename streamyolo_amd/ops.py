@@ -484,6 +484,14 @@ def bn_finalize_apply(ssum, ssq, count, gamma, beta, eps, scale, shift, mean, in
                                           y.pixels // nseg, y.C, y.dtype, nseg, stream_of(y.buf)), "sy_bn_finalize_apply")
 
 
+def bn_bwd_reduce_live_rows(pixels, C_, dtype, nseg=1):
+    """grid.x of a bn_silu_bwd_reduce launch under the cap in force now = the replica rows it can write (before `% copies`)."""
+    rows = C.c_int32(0)
+    check(_lib.lib().sy_bn_bwd_reduce_live_rows(int(pixels), int(C_), int(dtype), int(nseg), C.byref(rows)),
+          "sy_bn_bwd_reduce_live_rows")
+    return int(rows.value)
+
+
 class BnRunningTable:
     """Device table for sy_bn_running_update.  `modules` = [(bn_module, [(sum, sqsum, count[, copies, ld]), ...calls in order])];
     sum / sqsum start at the module's first channel; ld = replica pitch when they are a channel slice of a wider array."""
@@ -564,17 +572,20 @@ def bn_silu_bwd_reduce(y, da, scale, shift, mean, invstd, sums, nseg=1):
 
 
 def bn_silu_bwd_apply(y, da, scale, shift, mean, invstd, gamma, sums, dy, dgamma=None, dbeta=None, nseg=1,
-                      dres=None, dres_accumulate=False, atomic_param_grads=False, raw_moment=False):
+                      dres=None, dres_accumulate=False, atomic_param_grads=False, raw_moment=False, live=None):
     """dres: gradient View of the residual input (y = silu(bn(conv)) + res): written (or accumulated) with da in this pass.
-    raw_moment: row 1 of `sums` is sum dz*y (left by a data gradient's fused reduce, conv2d(bn_reduce=...)), not sum dz*xhat."""
+    raw_moment: row 1 of `sums` is sum dz*y (left by a data gradient's fused reduce, conv2d(bn_reduce=...)), not sum dz*xhat.
+    live: replica rows per segment written since the clear (bn_bwd_reduce_live_rows, capped at the rows allocated): the fold
+    stops there (sy_bn_silu_bwd_apply_live); None = all rows."""
     assert dres is None or (dres.C == y.C and dres.pixels == y.pixels)
-    check(_lib.lib().sy_bn_silu_bwd_apply(y.ptr(), y.ld, da.ptr(), da.ld, scale.data_ptr(), shift.data_ptr(),
-                                          mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), sums.data_ptr(),
-                                          sums.numel() // (2 * y.C * nseg), dy.ptr(), dy.ld, y.pixels // nseg, y.C,
-                                          _p(dgamma), _p(dbeta), None if dres is None else dres.ptr(),
-                                          0 if dres is None else dres.ld,
-                                          (1 if dres_accumulate else 0) | (2 if atomic_param_grads else 0) | (4 if raw_moment else 0), y.dtype, nseg,
-                                          stream_of(y.buf)), "sy_bn_silu_bwd_apply")
+    copies = sums.numel() // (2 * y.C * nseg)
+    check(_lib.lib().sy_bn_silu_bwd_apply_live(y.ptr(), y.ld, da.ptr(), da.ld, scale.data_ptr(), shift.data_ptr(),
+                                               mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), sums.data_ptr(),
+                                               copies, 0 if live is None else min(int(live), copies), dy.ptr(), dy.ld,
+                                               y.pixels // nseg, y.C, _p(dgamma), _p(dbeta),
+                                               None if dres is None else dres.ptr(), 0 if dres is None else dres.ld,
+                                               (1 if dres_accumulate else 0) | (2 if atomic_param_grads else 0) | (4 if raw_moment else 0), y.dtype, nseg,
+                                               stream_of(y.buf)), "sy_bn_silu_bwd_apply_live")
 
 
 def head_decode(out, hw=None, strides=None, boxes=True, obj_sigmoid=False, corners=False):

@@ -40,7 +40,9 @@ from .ops import View, EPI_LINEAR, CONV_DGRAD
 # the replicas every workgroup of the apply pass re-reads shrink 8x, and -216 launches on the forward chains); the run-to-run
 # reproducibility that argued for 32 replicas is the exact mode's business now (one replica row per workgroup, bit-equal steps).
 # Round 7: the per-workgroup rows are the default in every dtype (EXACT_STATS below), and the fused launch cannot fold them, so it
-# runs only with STREAMYOLO_EXACT_STATS=0 (l step, 8 pairs, bf16, same box: 22.35-22.53 ms deterministic vs 19.39-19.44 ms).
+# runs only with STREAMYOLO_EXACT_STATS=0 (l step, 8 pairs, bf16, same box: 22.35-22.53 ms deterministic vs 19.39-19.44 ms; round 12,
+# LIVE_ROWS below: 21.65-21.73 vs 20.05 on another box.  Round 12 also ran this launch behind a fold of the exact rows: 24.0 us per
+# launch against 7.7 + 12.0 for the two it replaces, the step no faster — profiles/r12 stage a).
 # "auto" (default): 16-bit compute dtypes only; "1" / "0": everywhere / nowhere (A/B timing).
 _FUSED_FINALIZE = __import__("os").environ.get("STREAMYOLO_FUSED_FINALIZE", "auto")
 # Round 5: the BatchNorm-backward REDUCE of a Bottleneck's 1x1 layer can ride in the epilogue of the 3x3 layer's data gradient (the
@@ -55,6 +57,18 @@ BNR_TILES = (98, 100, 101, 109, 104, 107, 117, 118)     # data-gradient tiles wh
 # the fp32 mode only: the 16-bit modes' shared replicas made the loss dict and SimOTA's decisions differ between identical steps);
 # "0" = the shared replica counts of the 16-bit speed modes (A/B switch)
 EXACT_STATS = __import__("os").environ.get("STREAMYOLO_EXACT_STATS", "1") != "0"
+# Round 12: the exact mode sizes the backward sums for the reduce cap (768 rows per layer and segment), but one reduce launch
+# writes only rows [0, its grid.x): 192 rows at C = 256, 96 at 512, 48 at 1024 (the cap is shared by the channel slices).  The
+# library reports that count from the launch's own geometry whenever the wrappers run (tuning step, every recording of a tape:
+# ops.bn_bwd_reduce_live_rows right behind the launch, under the cap in force THEN — a cap that changed between plan build and
+# recording is seen) and the replica fold in front of the apply pass stops at the last live row, sixteen loads in
+# flight per thread (sy_bn_silu_bwd_apply_live): the same additions in the same order — idle rows are +0.0f — so every output
+# bit is unchanged.  l step, 8 pairs, bf16, same box, same tiles, four alternations: 21.65-21.73 vs 23.27-23.28 ms
+# (fold_replicas 31.9 -> 9.0 us per launch, 216 launches on the frame chains; profiles/r12 stage b).  "0": the fold over all rows
+# (A/B switch and the reference of tests/test_bn_live_rows.py).
+# The forward counterpart (live rows of the convolution statistics + finalize inside the apply pass) was built, bit-equal and
+# measured in an alternation of its own: 22.57-22.80 vs 22.52-22.81 ms — no gain, removed again (profiles/r12 stage a).
+LIVE_ROWS = __import__("os").environ.get("STREAMYOLO_LIVE_ROWS", "1") != "0"
 # The workgroup cap of the BatchNorm-backward APPLY pass AS SCHEDULED in the step: the library's own default (1024) is that kernel's
 # optimum from round 2; beside round 5's frame chains and weight-gradient streams fewer, fatter workgroups leave the MFMA kernels
 # their CUs: 512 -> l step 20.83-20.88 vs 21.01-21.03 ms and 20.92 vs 21.00-21.14 on another box (256: 21.40-21.44; the forward apply
@@ -432,6 +446,7 @@ class TrainPlan:
         # (never with the exact mode's one-row-per-workgroup statistics: sy_bn_finalize_apply does not fold the thousands of rows —
         #  only sy_bn_finalize's fold_rows_kernel does, and the running-statistics launch reads the folded rows — ADVICE r05)
         self.fused_finalize = ((_FUSED_FINALIZE == "1") or (_FUSED_FINALIZE == "auto" and self.dtype != ops.DT_F32)) and not self.exact_stats
+        self.live_rows = LIVE_ROWS and self.exact_stats
         reduce_cap = _schedule_bn_caps()       # the library's own figure: one replica row per reduce workgroup in the exact mode
 
         def copies_of(op):
@@ -723,10 +738,13 @@ class TrainPlan:
         """BatchNorm.SiLU backward of one launch unit: the reduce pass (unless the data gradient that produced `da` carried it:
         op.bnr_by), then the apply pass."""
         fused = getattr(op, "bnr_by", None) is not None
+        live = None
         if not fused:
             ops.bn_silu_bwd_reduce(y, da, *aff, bsum, nseg=nseg)
+            if self.live_rows:      # the rows THAT launch wrote, from the library's own grid under the cap in force now
+                live = op.live_bwd = ops.bn_bwd_reduce_live_rows(y.pixels // nseg, y.C, y.dtype, nseg)
         ops.bn_silu_bwd_apply(y, da, *aff, gamma, bsum, dy, dgamma, dbeta, nseg=nseg, dres=dres, dres_accumulate=acc,
-                              atomic_param_grads=atomic, raw_moment=fused)
+                              atomic_param_grads=atomic, raw_moment=fused, live=live)
 
     def _bnr_producer(self, op, dx, acc, t):
         """The 1x1 ConvOp whose BatchNorm-backward reduce this op's data gradient can carry (SY_EPI_BNR), or None.  A static
