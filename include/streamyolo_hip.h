@@ -578,6 +578,56 @@ SY_API int sy_track_update(const float* det, const int32_t* cnt, int B, int max_
 SY_API int sy_track_forecast(const sy_track_query* queries, int n, const sy_track_state* state, const sy_track_params* params,
                              float* out, int32_t* out_id, int32_t* out_cnt, void* stream);
 
+/* ---- COCO-style scoring of detections on the device (AP / AR, the sAP numbers) ---------------------------------------
+ * Stands in for pycocotools' COCOeval on boxes, as the reference calls it (sAP/det/__init__.py::eval_ccf,
+ * exps/evaluators/onex_stream_evaluator.py): computeIoU + evaluateImg per (image, class) in sy_score_match, accumulate in
+ * sy_score_accumulate.  A scorer state is ONE device allocation of sy_score_state_bytes(num_classes, capacity):
+ *   int32 used[C] (records appended per class; may run past capacity once the overflow counter is set), int32 npig[C][4]
+ *   (non-ignored ground truths per class and area range), int32 overflow (records dropped for want of room), padding to a
+ *   multiple of 32 bytes, then C arenas of `capacity` records of 32 bytes:
+ *   uint32 score bits (float32, >= 0) | uint32 seq = image * 128 + rank | uint64 matched | uint64 ignored | int32 rank | int32 0
+ *   with bit (a * n_thr + t) of matched / ignored = evaluateImg's dtMatches != 0 / dtIgnore at area range a, threshold t.
+ * All IoU, precision and recall arithmetic is IEEE double in COCOeval's operation order on the thresholds the HOST supplies
+ * (np.linspace values, np.spacing(1)): results equal a float64 numpy restatement bit for bit, whatever order the workgroups
+ * ran in (integer atomics only; a record's position in its arena carries no meaning).  Added to ABI 7 (nothing existing
+ * changed). */
+#define SY_SCORE_MAX_THR 16         /* IoU thresholds                                                                    */
+#define SY_SCORE_MAX_AREA 4         /* area ranges                                                                       */
+#define SY_SCORE_MAX_MAXDET 4       /* maxDets entries, each in 1..SY_SCORE_MAX_DET                                      */
+#define SY_SCORE_MAX_REC 128        /* recall thresholds (ascending)                                                     */
+#define SY_SCORE_MAX_DET 100        /* detections kept per (image, class): the best by score, ties by input row          */
+#define SY_SCORE_MAX_GT 256         /* the compiled maximum of max_gt (ground truths per image)                          */
+#define SY_SCORE_LAYOUT_NMS 0       /* det [B, max_det, 7]: x1, y1, x2, y2, obj, class_conf, class; score = obj * class_conf (fp32) */
+#define SY_SCORE_LAYOUT_TRACK 1     /* det [B, max_det, 6]: x1, y1, x2, y2, score, label (sy_track_update's out)          */
+#define SY_SCORE_LAYOUT_XYWH 2      /* det [B, max_det, 6]: x, y, w, h, score, label (COCO result rows)                  */
+typedef struct sy_score_params {    /* HOST memory, copied into the launch                                               */
+    int32_t n_thr, n_rec, n_area, n_maxdet;
+    int32_t maxdet[SY_SCORE_MAX_MAXDET];
+    double eps;                     /* np.spacing(1)                                                                      */
+    double iou_thr[SY_SCORE_MAX_THR];
+    double area_lo[SY_SCORE_MAX_AREA], area_hi[SY_SCORE_MAX_AREA];   /* both ends inclusive                               */
+    double rec_thr[SY_SCORE_MAX_REC];
+} sy_score_params;
+/* bytes of a state / of the workspace of sy_score_accumulate (16 bytes per record slot, the capacity rounded up to a power of
+ * two); -1 for sizes out of range (num_classes in 1..65535, capacity >= 1, num_classes * capacity <= 2^30) */
+SY_API int64_t sy_score_state_bytes(int num_classes, int capacity);
+SY_API int64_t sy_score_workspace_bytes(int num_classes, int capacity);
+/* clears the counters of a state (the arenas need no clearing) */
+SY_API int sy_score_reset(void* state, int num_classes, int capacity, void* stream);
+/* One batch of images, B x num_classes workgroups of one wave: row b is image number image_base + b (< 2^25).  det / cnt [B]
+ * in `layout`; divisor: NULL or float32 [B], each coordinate is divided by divisor[b] in float32; then w = x2 - x1, h = y2 - y1
+ * in float32, everything else in double.  gt [B, max_gt, 7] float64: x, y, w, h, class, iscrowd, area; gt_cnt int32 [B].
+ * B == 0 does nothing. */
+SY_API int sy_score_match(const float* det, const int32_t* cnt, int B, int max_det, int layout, const float* divisor,
+                          const double* gt, const int32_t* gt_cnt, int max_gt, int64_t image_base,
+                          const sy_score_params* params, void* state, int num_classes, int capacity, void* stream);
+/* precision [n_thr, n_rec, num_classes, n_area, n_maxdet] and recall [n_thr, num_classes, n_area, n_maxdet] (float64, every
+ * entry written; -1 where a class has no non-ignored ground truth in the area range) from the state, which is only read.
+ * One workgroup per class sorts the class's records in `workspace` (sy_score_workspace_bytes).  overflow: NULL, or one double
+ * that receives the state's overflow counter (placed behind recall it travels in the caller's one copy of the results). */
+SY_API int sy_score_accumulate(const void* state, int num_classes, int capacity, const sy_score_params* params, void* workspace,
+                               double* precision, double* recall, double* overflow, void* stream);
+
 /* backward of sy_resize_nearest (scatter-add into the source grid) */
 SY_API int sy_resize_nearest_bwd(const void* dout, int N, int Ho, int Wo, int C, int lddo, int64_t dobs,
                           void* din, int Hi, int Wi, int lddi, int64_t dibs, int accumulate,

@@ -14,9 +14,10 @@ from .model.yolox import YOLOX
 from .postprocess import postprocess
 from .data import Surface
 from .streaming import MultiStreamDetector, StreamingDetector, TrackConfig
+from .scoring import DetectionScorer, score_coco
 
 __all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model", "DeviceGradScaler",
-           "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig"]
+           "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig", "DetectionScorer", "score_coco"]
 __version__ = "0.1.0"
 
 MODEL_ZOO = {

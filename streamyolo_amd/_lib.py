@@ -129,6 +129,18 @@ class TrackState(C.Structure):
 
 TRACK_MAX_TRACKS = 256                         # SY_TRACK_MAX_TRACKS
 
+SCORE_MAX_THR, SCORE_MAX_AREA, SCORE_MAX_MAXDET, SCORE_MAX_REC, SCORE_MAX_DET, SCORE_MAX_GT = 16, 4, 4, 128, 100, 256   # SY_SCORE_MAX_*
+SCORE_LAYOUT = {"nms": 0, "track": 1, "xywh": 2}          # SY_SCORE_LAYOUT_*
+SCORE_RECORD = [("score_bits", "<u4"), ("seq", "<u4"), ("matched", "<u8"), ("ignored", "<u8"), ("rank", "<i4"), ("reserved", "<i4")]
+
+
+class ScoreParams(C.Structure):
+    """sy_score_params (include/streamyolo_hip.h)."""
+    _fields_ = [("n_thr", C.c_int32), ("n_rec", C.c_int32), ("n_area", C.c_int32), ("n_maxdet", C.c_int32),
+                ("maxdet", C.c_int32 * SCORE_MAX_MAXDET), ("eps", C.c_double), ("iou_thr", C.c_double * SCORE_MAX_THR),
+                ("area_lo", C.c_double * SCORE_MAX_AREA), ("area_hi", C.c_double * SCORE_MAX_AREA),
+                ("rec_thr", C.c_double * SCORE_MAX_REC)]
+
 
 def pack_table(rows):
     """ctypes array of PackEntry with the tile0 prefix filled in -> (array, total_tiles)."""
@@ -194,6 +206,11 @@ SIGNATURES = {
     "sy_stream_state_scatter": (_I, [_P, _I, _I, _I, _P, _I, _P]),
     "sy_track_update": (_I, [_P, _P, _I, _I, _P, _P, _P, C.POINTER(TrackState), C.POINTER(TrackParams), _P, _P, _P, _P]),
     "sy_track_forecast": (_I, [_P, _I, C.POINTER(TrackState), C.POINTER(TrackParams), _P, _P, _P, _P]),
+    "sy_score_state_bytes": (_L, [_I, _I]),
+    "sy_score_workspace_bytes": (_L, [_I, _I]),
+    "sy_score_reset": (_I, [_P, _I, _I, _P]),
+    "sy_score_match": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _L, C.POINTER(ScoreParams), _P, _I, _I, _P]),
+    "sy_score_accumulate": (_I, [_P, _I, _I, C.POINTER(ScoreParams), _P, _P, _P, _P, _P]),
     "sy_splitk_epilogue": (_I, [_P, _I, _L, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "sy_rows_add_f32": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
     "sy_pred_grad_fold_workspace_floats": (_L, [_I]),

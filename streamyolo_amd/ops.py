@@ -445,6 +445,91 @@ def track_forecast(queries, n, state, params, out, out_id, out_cnt):
     return out, out_id, out_cnt
 
 
+def score_params(iou_thr, rec_thr, area_rng, max_dets, eps):
+    """sy_score_params from the HOST's values (the kernels never recompute a threshold): sequences of float64."""
+    p = _lib.ScoreParams()
+    iou_thr, rec_thr, max_dets = [float(v) for v in iou_thr], [float(v) for v in rec_thr], [int(v) for v in max_dets]
+    area_rng = [(float(lo), float(hi)) for lo, hi in area_rng]
+    assert 1 <= len(iou_thr) <= _lib.SCORE_MAX_THR and 1 <= len(rec_thr) <= _lib.SCORE_MAX_REC
+    assert 1 <= len(area_rng) <= _lib.SCORE_MAX_AREA and 1 <= len(max_dets) <= _lib.SCORE_MAX_MAXDET
+    p.n_thr, p.n_rec, p.n_area, p.n_maxdet, p.eps = len(iou_thr), len(rec_thr), len(area_rng), len(max_dets), float(eps)
+    for i, v in enumerate(iou_thr):
+        p.iou_thr[i] = v
+    for i, v in enumerate(rec_thr):
+        p.rec_thr[i] = v
+    for i, (lo, hi) in enumerate(area_rng):
+        p.area_lo[i], p.area_hi[i] = lo, hi
+    for i, v in enumerate(max_dets):
+        p.maxdet[i] = v
+    return p
+
+
+def score_state_bytes(num_classes, capacity):
+    n = _lib.lib().sy_score_state_bytes(int(num_classes), int(capacity))
+    if n < 0:
+        raise ValueError("scorer state of %r classes x %r records is out of range" % (num_classes, capacity))
+    return int(n)
+
+
+def score_workspace_bytes(num_classes, capacity):
+    n = _lib.lib().sy_score_workspace_bytes(int(num_classes), int(capacity))
+    if n < 0:
+        raise ValueError("scorer workspace of %r classes x %r records is out of range" % (num_classes, capacity))
+    return int(n)
+
+
+def _score_state(state, num_classes, capacity):
+    assert state.dtype == torch.uint8 and state.is_contiguous() and state.numel() >= score_state_bytes(num_classes, capacity)
+
+
+def score_reset(state, num_classes, capacity):
+    """Clears the counters of a scorer state (uint8 tensor of score_state_bytes; see the header for its layout)."""
+    _score_state(state, num_classes, capacity)
+    check(_lib.lib().sy_score_reset(state.data_ptr(), int(num_classes), int(capacity), stream_of(state)), "sy_score_reset")
+
+
+def score_match(det, cnt, gt, gt_cnt, image_base, params, state, num_classes, capacity, divisor=None, rows=None, layout="nms"):
+    """COCOeval's computeIoU + evaluateImg for rows 0..rows-1 of one batch as images image_base.. (sy_score_match): det fp32
+    [B, D, 7] ("nms": x1, y1, x2, y2, obj, class_conf, class) or [B, D, 6] ("track": x1, y1, x2, y2, score, label; "xywh": x, y, w, h, score, label), cnt int32 [B],
+    divisor None or fp32 [B], gt float64 [B, G, 7] (x, y, w, h, class, iscrowd, area), gt_cnt int32 [B].  Appends to `state`."""
+    code = _lib.SCORE_LAYOUT[layout]
+    assert det.dtype == torch.float32 and det.is_contiguous() and det.dim() == 3 and det.shape[2] == (6 if code else 7)
+    B = det.shape[0] if rows is None else int(rows)
+    dev = state.device
+    assert 0 <= B <= det.shape[0] and det.device == dev
+    assert cnt.dtype == torch.int32 and cnt.is_contiguous() and cnt.numel() >= B and cnt.device == dev
+    assert gt.dtype == torch.float64 and gt.is_contiguous() and gt.dim() == 3 and gt.shape[2] == 7 and gt.shape[0] >= B
+    assert gt.device == dev and gt_cnt.dtype == torch.int32 and gt_cnt.is_contiguous() and gt_cnt.numel() >= B and gt_cnt.device == dev
+    if divisor is not None:
+        assert divisor.dtype == torch.float32 and divisor.is_contiguous() and divisor.numel() >= B and divisor.device == dev
+    _score_state(state, num_classes, capacity)
+    check(_lib.lib().sy_score_match(det.data_ptr(), cnt.data_ptr(), B, det.shape[1], code,
+                                    divisor.data_ptr() if divisor is not None else None, gt.data_ptr(), gt_cnt.data_ptr(),
+                                    gt.shape[1], int(image_base), C.byref(params), state.data_ptr(), int(num_classes),
+                                    int(capacity), stream_of(det)), "sy_score_match")
+
+
+def score_accumulate(state, num_classes, capacity, params, workspace, precision, recall, overflow=None):
+    """precision float64 [T, R, K, A, M] and recall float64 [T, K, A, M] of a scorer state (sy_score_accumulate); workspace: uint8
+    tensor of score_workspace_bytes; overflow: None or a float64 tensor of one element that receives the overflow counter.  The
+    state is only read."""
+    _score_state(state, num_classes, capacity)
+    dev = state.device
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.device == dev
+    assert workspace.numel() >= score_workspace_bytes(num_classes, capacity)
+    T, R, K, A, M = params.n_thr, params.n_rec, int(num_classes), params.n_area, params.n_maxdet
+    assert precision.dtype == torch.float64 and precision.is_contiguous() and tuple(precision.shape) == (T, R, K, A, M)
+    assert recall.dtype == torch.float64 and recall.is_contiguous() and tuple(recall.shape) == (T, K, A, M)
+    assert precision.device == dev and recall.device == dev
+    if overflow is not None:
+        assert overflow.dtype == torch.float64 and overflow.numel() == 1 and overflow.device == dev
+    check(_lib.lib().sy_score_accumulate(state.data_ptr(), K, int(capacity), C.byref(params), workspace.data_ptr(),
+                                         precision.data_ptr(), recall.data_ptr(),
+                                         overflow.data_ptr() if overflow is not None else None, stream_of(state)),
+          "sy_score_accumulate")
+    return precision, recall
+
+
 def rows_add_f32(dst, src, rows, cols, ldd, lds, zero_src=False):
     """dst[r][:cols] += src[r][:cols] (fp32, row pitches ldd / lds in elements); zero_src: clear the source behind the read."""
     assert dst.dtype == torch.float32 and src.dtype == torch.float32

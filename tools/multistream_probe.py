@@ -43,6 +43,13 @@ a tree that has no tracker.
 
     python tools/multistream_probe.py --track 1 --batches 1,8
     python tools/multistream_probe.py --track 1 --untracked-only 1 --tree _base --batches 1,8
+
+--score 1: the tick of one detector with and without DetectionScorer.add behind it (sy_score_match on the tick's device tensors,
+twelve synthetic ground truths per row; `add` is not on the tape), alternating: `tick_ms_per_tick`, `tick_add_ms_per_tick`, the
+per-round times and `add_ms_per_tick` (best minus best, to be read against the spread); then `summarize_ms`: the wall time of
+one summarize() over everything the timed ticks added (sy_score_accumulate + the evaluation's host read).
+
+    python tools/multistream_probe.py --score 1 --batches 1,8
 """
 import argparse
 import json
@@ -78,6 +85,7 @@ def main():
     ap.add_argument("--staged-only", type=int, default=0, help="with --surfaces 1: only the staged tick (runs on older trees)")
     ap.add_argument("--track", type=int, default=0, help="1: the tracked tick beside the untracked tick of the same batch")
     ap.add_argument("--untracked-only", type=int, default=0, help="with --track 1: only the untracked tick (runs on older trees)")
+    ap.add_argument("--score", type=int, default=0, help="1: the tick with and without DetectionScorer.add, and one summarize()")
     ap.add_argument("--tree", default=None, help="root of another checkout of the repository to import the package from")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -265,6 +273,57 @@ def main():
             res["rows"].append(row)
             emit()
             del ticks, plain
+        print(emit())
+        return
+
+    if args.score:
+        if args.mixed or args.surfaces or args.track or fmt != "bgr":
+            ap.error("--score is a separate measurement")
+        from streamyolo_amd.scoring import DetectionScorer
+        from streamyolo_amd.streaming import MultiStreamDetector
+        res.update({"score": True})
+        for B in batches:
+            det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+            det.warm_up(args.warmup)
+            sids = [det.open() for _ in range(B)]
+            n_img = B * (args.ticks + 1) * args.rounds + B
+            scorer = DetectionScorer(8, capacity=min(100 * n_img, 1 << 20), max_gt=16, device=dev)
+            # ground truth: twelve fixed boxes per row in camera coordinates, classes cycling
+            g = torch.arange(12, dtype=torch.float64)
+            gt = torch.stack([100.0 + 140.0 * g, 80.0 + 60.0 * g, 60.0 + 10.0 * g, 50.0 + 8.0 * g, g % 8, torch.zeros(12).double(),
+                              (60.0 + 10.0 * g) * (50.0 + 8.0 * g)], dim=1)
+            gt = torch.cat([gt, torch.zeros((4, 7), dtype=torch.float64)]).repeat(B, 1, 1).contiguous().to(dev)
+            gcnt = torch.full((B,), 12, dtype=torch.int32, device=dev)
+            divisor = torch.full((B,), det._geom[sids[0]][2], dtype=torch.float32, device=dev)
+
+            def tick():
+                det.detect_device(frames[:B], sids)
+
+            def tick_add():
+                d, c, n = det.detect_device(frames[:B], sids)
+                scorer.add(d, c, gt, gcnt, divisor=divisor, rows=n)
+            ticks = {"tick": tick, "tick_add": tick_add}
+            rounds = {k: [] for k in ticks}
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                for k, fn in ticks.items():
+                    fn()
+                    rounds[k].append(timed(fn, args.ticks)[0])
+            row = {"batch": B, "active": B}
+            for k, v in rounds.items():
+                row.update({k + "_ms_per_tick": min(v), k + "_ms_rounds": v, k + "_spread_ms": max(v) - min(v)})
+            row["add_ms_per_tick"] = min(rounds["tick_add"]) - min(rounds["tick"])
+            row["detections_per_row"] = det.detect_device(frames[:B], sids)[1][:B].cpu().tolist()
+            walls = []
+            for _ in range(args.rounds):                         # summarize() twice and more: the first call allocates its workspace
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = scorer.summarize()
+                walls.append((time.perf_counter() - t0) * 1e3)
+            row.update({"summarize_ms": min(walls), "summarize_ms_rounds": walls, "images_scored": scorer.images,
+                        "records_per_class": scorer.counters()[0].tolist(), "AP": out["AP"], "AR100": out["AR100"]})
+            res["rows"].append(row)
+            emit()
+            del det, scorer
         print(emit())
         return
 
