@@ -22,6 +22,7 @@ sync-free fast path bench.py and a native trainer use.
 """
 import ctypes as C
 import os
+import time
 
 import torch
 
@@ -32,31 +33,10 @@ from .model.plan_cache import compute_dtype_for
 from .ops import View, EPI_LINEAR, CONV_DGRAD
 
 
-# one launch for BatchNorm finalize + BN.SiLU apply (sy_bn_finalize_apply); "0": the two separate launches (A/B timing)
-# (default off: kernel time 2.77 vs 2.90 ms per l step, but the step itself is not faster at 32 statistic replicas, and the 8
-# replicas that make it 0.1-0.26 ms faster break the 1e-5 run-to-run reproducibility of the fp16 step — profiles/r02/t_*, u_*,
-# profiles/r04/d_bench_ff8.json)
-# Round 5: ON for the 16-bit modes together with 4 statistic replicas (l step 20.46-20.50 vs 20.64-20.67 ms, profiles/r05 stage l:
-# the replicas every workgroup of the apply pass re-reads shrink 8x, and -216 launches on the forward chains); the run-to-run
-# reproducibility that argued for 32 replicas is the exact mode's business now (one replica row per workgroup, bit-equal steps).
-# Round 7: the per-workgroup rows are the default in every dtype (EXACT_STATS below), and the fused launch cannot fold them, so it
-# runs only with STREAMYOLO_EXACT_STATS=0 (l step, 8 pairs, bf16, same box: 22.35-22.53 ms deterministic vs 19.39-19.44 ms; round 12,
-# LIVE_ROWS below: 21.65-21.73 vs 20.05 on another box.  Round 12 also ran this launch behind a fold of the exact rows: 24.0 us per
-# launch against 7.7 + 12.0 for the two it replaces, the step no faster — profiles/r12 stage a).
-# "auto" (default): 16-bit compute dtypes only; "1" / "0": everywhere / nowhere (A/B timing).
-_FUSED_FINALIZE = __import__("os").environ.get("STREAMYOLO_FUSED_FINALIZE", "auto")
-# Round 5: the BatchNorm-backward REDUCE of a Bottleneck's 1x1 layer can ride in the epilogue of the 3x3 layer's data gradient (the
-# only producer of its activation gradient: engine.ConvOp.pre_op) — sy_conv2d's SY_EPI_BNR; 72 launches and one read of dA less per
-# l step.  16-bit modes, frames as stream-parallel chains (per-frame launches).  Built, parity-green (kernel + model tests on the
-# MI355X) and measured: OFF by default — the reduce pass leaves the chains (-0.87 ms of kernel time), but its sigmoid / product work
-# (80 values per lane) then runs in the epilogue of a one-wave-per-SIMD MFMA kernel instead of in a memory-bound launch that other
-# kernels overlap: data gradients +0.6 ms, the l step 20.78-20.82 vs 20.68-20.75 ms (profiles/r05 stage m).  "1": on (A/B timing).
-BNR_FUSION = __import__("os").environ.get("STREAMYOLO_BNR_FUSION", "0") != "0"
-BNR_TILES = (98, 100, 101, 109, 104, 107, 117, 118)     # data-gradient tiles whose staged epilogue carries it (csrc/conv_igemm.hip)
 # one statistics replica row per workgroup -> run-to-run bit-equal steps in every compute dtype (TrainPlan.__init__; until round 7
 # the fp32 mode only: the 16-bit modes' shared replicas made the loss dict and SimOTA's decisions differ between identical steps);
 # "0" = the shared replica counts of the 16-bit speed modes (A/B switch)
-EXACT_STATS = __import__("os").environ.get("STREAMYOLO_EXACT_STATS", "1") != "0"
+EXACT_STATS = os.environ.get("STREAMYOLO_EXACT_STATS", "1") != "0"
 # Round 12: the exact mode sizes the backward sums for the reduce cap (768 rows per layer and segment), but one reduce launch
 # writes only rows [0, its grid.x): 192 rows at C = 256, 96 at 512, 48 at 1024 (the cap is shared by the channel slices).  The
 # library reports that count from the launch's own geometry whenever the wrappers run (tuning step, every recording of a tape:
@@ -68,7 +48,7 @@ EXACT_STATS = __import__("os").environ.get("STREAMYOLO_EXACT_STATS", "1") != "0"
 # (A/B switch and the reference of tests/test_bn_live_rows.py).
 # The forward counterpart (live rows of the convolution statistics + finalize inside the apply pass) was built, bit-equal and
 # measured in an alternation of its own: 22.57-22.80 vs 22.52-22.81 ms — no gain, removed again (profiles/r12 stage a).
-LIVE_ROWS = __import__("os").environ.get("STREAMYOLO_LIVE_ROWS", "1") != "0"
+LIVE_ROWS = os.environ.get("STREAMYOLO_LIVE_ROWS", "1") != "0"
 # The workgroup cap of the BatchNorm-backward APPLY pass AS SCHEDULED in the step: the library's own default (1024) is that kernel's
 # optimum from round 2; beside round 5's frame chains and weight-gradient streams fewer, fatter workgroups leave the MFMA kernels
 # their CUs: 512 -> l step 20.83-20.88 vs 21.01-21.03 ms and 20.92 vs 21.00-21.14 on another box (256: 21.40-21.44; the forward apply
@@ -282,8 +262,7 @@ class StagedWeights:
         return w_ro, b_ro, w_c, b_c.detach(), w_ro_t, w_c_t
 
 
-CSP_FORK = os.environ.get("STREAMYOLO_CSP_FORK", "1") != "0"
-MERGE_SIBLINGS_TRAIN = os.environ.get("STREAMYOLO_MERGE_TRAIN", "1") != "0"
+# (Schedules that earlier rounds built, measured and settled no longer have switches here: DESIGN.md §6, "Switches retired in round 14".)
 # VERDICT r02 "next" #3, measured NEGATIVE (profiles/r03/e_*): with the producer's BatchNorm.SiLU applied by the 3x3 consumer in
 # LDS the l step takes 24.90-24.93 ms against 24.10 ms on the same box — the normalising halo kernel costs 12-22 us more per
 # launch than the plain one (+20-30 %: the extra LDS round trip and barrier per channel slab are not hidden), about what the
@@ -300,13 +279,6 @@ FWD_SPLIT_FRAMES = os.environ.get("STREAMYOLO_FWD_SPLIT_FRAMES", "1") != "0"
 # s 8.05 vs 7.96 — it pays once a frame's layers are big enough to keep the chip busy in half-size launches: "auto" turns it on
 # for B * H * W * width^2 >= 2e6 (l from 4 pairs, m from 8 at 600x960; not s).  "1" / "0" force it.
 BWD_SPLIT_FRAMES = os.environ.get("STREAMYOLO_BWD_SPLIT_FRAMES", "auto")
-# On the same machinery: head levels 1-2 backward as a chain of their own (stream 2) beside level 0; weight gradients alternating
-# between two streams (1 and 3, a split-K workspace each) so that one layer's fold runs beside the next layer's wgrad.  Measured
-# on one box (profiles/r03/l_*): 22.66-22.77 (neither) / 22.73 (head chain) / 22.54 (two wgrad streams) / 22.27 ms (both).
-HEAD_BWD_CHAINS = os.environ.get("STREAMYOLO_HEAD_BWD_CHAINS", "1") != "0"
-# Round 5, forward: a head level (+ its two DFP fusion convs) starts as soon as its PAN output exists in both frames, on a third
-# chain beside the rest of the frame chains (TrainPlan._early_levels).  "0": the levels behind the join of the frame chains.
-HEAD_EARLY = os.environ.get("STREAMYOLO_HEAD_EARLY", "1") != "0"
 # Round 6: stream-wait packets on the frame chains are not free.  A timing experiment that dropped every ring-slot event of the
 # backward pass (results invalid, profiles/r06 stage u) ran the l step in 20.39 instead of 21.09 ms, dropping the chain -> weight-gradient
 # dependencies on top 20.12-20.17: each hipStreamWaitEvent is a barrier packet the chain's queue stops at (~3 us), signalled or not,
@@ -321,8 +293,8 @@ SLOT_BATCH = max(1, int(os.environ.get("STREAMYOLO_SLOT_BATCH", "3")))
 # (The chain -> weight-gradient dependencies were sized the same way — 0.3 ms without them, stage x — but they are real dependencies,
 #  not packet overhead: issuing the split backward's weight gradients in batches of 2 ... 6 layers behind ONE event per chain bought
 #  nothing, 20.12-20.24 vs 20.11-20.12 ms, stage y; removed.)
-DUAL_WGRAD = os.environ.get("STREAMYOLO_DUAL_WGRAD", "1") != "0"
-WGRAD_STREAMS = [1, 3, 4, 5][:max(1, min(4, int(os.environ.get("STREAMYOLO_WGRAD_STREAMS", "2")) if DUAL_WGRAD else 1))]
+# weight gradients alternate between these two streams (a split-K workspace each): one layer's fold runs beside the next layer's wgrad
+WGRAD_STREAMS = [1, 3]
 # (Weight gradients on streams of their own instead of sharing stream 1 with the forward pass's support-frame chain, with or without
 # a low hardware queue priority: 22.78-22.79 vs 22.70 ms — profiles/r04/b_bench_ownw*.json — removed.)
 
@@ -371,7 +343,7 @@ def _csp_role(tag):
 class TrainPlan:
     # replicas of each BN-backward reduction: 2, folded by every workgroup of the apply pass itself (no fold launch);
     # measured 28.3 vs 28.6 ms per l step against 16 replicas + fold kernel (profiles/r01/f_*)
-    BWD_COPIES = int(os.environ.get("STREAMYOLO_BWD_COPIES", "2"))
+    BWD_COPIES = 2
     # replicas of each conv's sum / sum^2 arrays: 4 are as fast as 32 but the longer fp32 atomic chains make the batch
     # variance (E[y^2] - mean^2) visibly order-dependent (tape-replay test: 1e-4 instead of 1e-6 between identical steps)
     # (round 5: 4 in the 16-bit modes — there the order noise is far below the rounding step, and the fused finalize + apply launch
@@ -385,8 +357,7 @@ class TrainPlan:
     # with the ring and the cheapest event schedule, 0.7 ms (8 pairs) / 0.9 ms (4 pairs) shorter than rounds 3-5's (profiles/r06
     # stages u-w).  RING > 0 keeps the ring (memory-tight hosts, A/B timing).
     RING = int(os.environ.get("STREAMYOLO_RING", "0"))
-    STREAMS = int(os.environ.get("STREAMYOLO_STREAMS", "2"))   # 1: everything on the caller's stream
-    TAPE_ON_CPU = True           # the SIMT-emulator test runs replay launch tapes too (same code path as the GPU)
+    STREAMS = 2                  # 1: everything on the caller's stream
 
     def __init__(self, model, B, H, W, dtype, device, parts="full", feat_shapes=None, pool=None):
         """parts: "full" = YOLOX (backbone + head, the fused forward + loss + backward plan); "backbone" = a DFPPAFPN alone
@@ -405,7 +376,7 @@ class TrainPlan:
         b = _PairBuilder(self.dtype, device)
         # sibling convolutions (CSP conv2 || conv1, the first cls / reg tower conv of a head level) as ONE conv / BatchNorm /
         # dgrad / wgrad launch each, as in the inference plans (engine.MergedConv): -88 launches per l step, no `+=` dgrad pass
-        b.merge_siblings = MERGE_SIBLINGS_TRAIN
+        b.merge_siblings = True
         if pafpn is not None:
             self.f0_cur, cur = build_frame_net(b, pafpn, B, H, W)          # current frame  (dfp_pafpn.py:120-140)
             self.n_frame_ops = len(b.ops)
@@ -443,9 +414,10 @@ class TrainPlan:
         # ceil(W / 32), whatever tile the tuner picks); backward reduce = its workgroup cap (SY_BN_REDUCE_BLOCKS, 768).
         self.exact_stats = EXACT_STATS
         self.stat_copies = self.STAT_COPIES if self.STAT_COPIES > 0 else (32 if self.dtype == ops.DT_F32 else 4)
-        # (never with the exact mode's one-row-per-workgroup statistics: sy_bn_finalize_apply does not fold the thousands of rows —
-        #  only sy_bn_finalize's fold_rows_kernel does, and the running-statistics launch reads the folded rows — ADVICE r05)
-        self.fused_finalize = ((_FUSED_FINALIZE == "1") or (_FUSED_FINALIZE == "auto" and self.dtype != ops.DT_F32)) and not self.exact_stats
+        # one launch for BatchNorm finalize + BN.SiLU apply (sy_bn_finalize_apply) in the 16-bit speed modes, never with the exact
+        # mode's one-row-per-workgroup statistics: sy_bn_finalize_apply does not fold the thousands of rows — only sy_bn_finalize's
+        # fold_rows_kernel does, and the running-statistics launch reads the folded rows
+        self.fused_finalize = (not self.exact_stats) and self.dtype != ops.DT_F32
         self.live_rows = LIVE_ROWS and self.exact_stats
         reduce_cap = _schedule_bn_caps()       # the library's own figure: one replica row per reduce workgroup in the exact mode
 
@@ -501,9 +473,9 @@ class TrainPlan:
         self.side = torch.cuda.Stream(device=device) if (device.type == "cuda" and self.STREAMS > 1) else None
         w_ = float(getattr(pafpn, "width", 1.0)) if pafpn is not None else 0.0
         self.bwd_split = (BWD_SPLIT_FRAMES == "1") or (BWD_SPLIT_FRAMES == "auto" and B * H * W * w_ * w_ >= 2.0e6)
-        self.side2 = torch.cuda.Stream(device=device) if (self.side is not None and (self.bwd_split or HEAD_BWD_CHAINS)) else None
-        self.side_w = {k: torch.cuda.Stream(device=device) for k in WGRAD_STREAMS[1:]} if self.side is not None else {}
-        self.side3 = self.side_w.get(3)
+        # streams 2 (support-frame chain of the split backward, head levels 1-2, early head levels) and 3 (second weight-gradient stream)
+        self.side2 = torch.cuda.Stream(device=device) if self.side is not None else None
+        self.side3 = torch.cuda.Stream(device=device) if self.side is not None else None
         self._chain, self._wg_stream, self._wg_flip = 0, 1, 0
         self.tuned = False                    # the first step (autotuning) runs on one stream
         self.force_serial = False             # profile(): per-kernel durations without overlap
@@ -644,7 +616,7 @@ class TrainPlan:
         if FWD_SPLIT_FRAMES and nf:
             # the two frames as two independent chains, current frame on the main stream, support frame on the side stream,
             # issued alternately (half-size launches, but one chain's tails and BatchNorm passes fill the other's gaps)
-            early = self._early_levels() if (HEAD_EARLY and self.head is not None and self.side2 is not None) else {}
+            early = self._early_levels() if (self.head is not None and self.side2 is not None) else {}
             self._mark("fork")
             for i in range(nf):
                 self._forward_op(self.ops[i])
@@ -675,15 +647,15 @@ class TrainPlan:
             if a.kind == "conv":
                 # CSPLayer: conv2(x) only meets the bottleneck chain conv1(x) -> m(...) again in conv3(cat[...]) —
                 # it runs on the side stream (idle during forward) beside the chain and joins before conv3
-                role = _csp_role(a.tag) if CSP_FORK else None
+                role = _csp_role(a.tag)
                 if role == "conv2":
                     self._mark("side")
-                    self._forward_pair(a)
-                    self._mark("main", None)
-                    continue
-                if role == "conv3":
+                elif role == "conv3":
                     self._mark("join")
-                self._forward_pair(a)
+                self._base_conv(a, a.x.pair(), a.yraw.pair(), a.y.pair(), None if a.res is None else a.res.pair(),
+                                a.unit[:2], a.unit[3], nseg=2)
+                if role == "conv2":
+                    self._mark("main", None)
             else:
                 self._forward_op(a)
                 self._forward_op(b2)
@@ -734,53 +706,62 @@ class TrainPlan:
         g, b_ = self.cache.bn[id(op.mod)]
         return g, b_, bn.eps, mom
 
-    def _bn_bwd(self, op, y, da, aff, gamma, bsum, dy, dgamma, dbeta, nseg=1, dres=None, acc=False, atomic=False):
-        """BatchNorm.SiLU backward of one launch unit: the reduce pass (unless the data gradient that produced `da` carried it:
-        op.bnr_by), then the apply pass."""
-        fused = getattr(op, "bnr_by", None) is not None
-        live = None
-        if not fused:
-            ops.bn_silu_bwd_reduce(y, da, *aff, bsum, nseg=nseg)
-            if self.live_rows:      # the rows THAT launch wrote, from the library's own grid under the cap in force now
-                live = op.live_bwd = ops.bn_bwd_reduce_live_rows(y.pixels // nseg, y.C, y.dtype, nseg)
-        ops.bn_silu_bwd_apply(y, da, *aff, gamma, bsum, dy, dgamma, dbeta, nseg=nseg, dres=dres, dres_accumulate=acc,
-                              atomic_param_grads=atomic, raw_moment=fused, live=live)
-
-    def _bnr_producer(self, op, dx, acc, t):
-        """The 1x1 ConvOp whose BatchNorm-backward reduce this op's data gradient can carry (SY_EPI_BNR), or None.  A static
-        property of the plan (the tapes record the decision): op reads ONLY that layer's activation, first write of its
-        gradient, 16-bit compute, a tile with the staged 128-channel epilogue, the raw output laid out like the gradient view."""
-        pre = op.pre_op
-        if (not BNR_FUSION or pre is None or acc or self.dtype == ops.DT_F32 or t not in BNR_TILES or op.k != 3 or op.stride != 1
-                or pre.res is not None or pre.yraw is None or pre.yraw.ld != dx.ld or pre.yraw.bs != dx.bs or pre.y.C % 8 or dx.ld % 8
-                or (dx.ptr() | pre.yraw.ptr()) % 16 or dx.bs % 8):     # sy_conv2d's own precondition of the staged epilogue (ADVICE r05)
-            return None
-        return pre
-
     def _bn_grads(self, op):
         """(dgamma, dbeta) arena views starting at the op's first part (the parts' slots are adjacent: see the arena order)."""
         bn = base_convs(op.mod)[0].bn
         return self.gview[id(bn.weight)], self.gview[id(bn.bias)]
 
-    def _forward_pair(self, a):
-        """BaseConv of the shared per-frame network on both frames: conv (+ per-frame statistics), finalize, BN+SiLU."""
-        gamma, beta, eps, mom = self._bn_params(a)
-        x2, raw2, y2 = a.x.pair(), a.yraw.pair(), a.y.pair()
-        u_sum, u_sq, _, (scale, shift, mean, invstd) = a.unit
-        t = a._tiles.get("fwd_stats2")
+    def _bn_bwd(self, op, y, da, aff, gamma, bsum, dy, dgamma, dbeta, nseg=1, dres=None, acc=False, atomic=False):
+        """BatchNorm.SiLU backward of one launch unit: the reduce pass, then the apply pass."""
+        ops.bn_silu_bwd_reduce(y, da, *aff, bsum, nseg=nseg)
+        live = None
+        if self.live_rows:          # the rows THAT launch wrote, from the library's own grid under the cap in force now
+            live = op.live_bwd = ops.bn_bwd_reduce_live_rows(y.pixels // nseg, y.C, y.dtype, nseg)
+        ops.bn_silu_bwd_apply(y, da, *aff, gamma, bsum, dy, dgamma, dbeta, nseg=nseg, dres=dres, dres_accumulate=acc,
+                              atomic_param_grads=atomic, live=live)
+
+    # ---- one body per launch kind -----------------------------------------------------------------------------------------
+    def _weights(self, mod, tile, transpose=False):
+        """(weight operand, its fragment-packed layout or None) of a convolution launch on tile code `tile`."""
+        return (self.cache.conv_weight(mod, transpose),
+                self.cache.conv_weight_frag(mod, transpose) if tile >= ops.TILE_WR else None)
+
+    def _tile(self, op, kind, nseg=1):
+        """Tuned kernel variant ('fwd_stats' / 'dgrad') of the op's launch over one frame (engine.ConvOp.tile) or over both frames
+        of the pair in one launch (nseg = 2: twice the images)."""
+        if nseg == 1:
+            return op.tile(kind)
+        t = op._tiles.get(kind + "2")
         if t is None:
-            t = ops.tuned_tile(ops.CONV_FWD, x2.dtype, x2.N, x2.H, x2.W, x2.C, y2.C, a.k, a.stride, self.device,
-                               with_stats=True)
-            a._tiles["fwd_stats2"] = t
-        ops.conv2d(x2, self.cache.conv_weight(a.mod), raw2, a.k, a.stride, stats=(u_sum, u_sq), tile=t,
-                   wfrag=self.cache.conv_weight_frag(a.mod) if t >= ops.TILE_WR else None, segments=2)
+            x, y = op.x, op.y
+            if kind == "dgrad":
+                t = ops.tuned_tile(CONV_DGRAD, y.dtype, 2 * y.N, y.H, y.W, y.C, x.C, op.k, op.stride, self.device)
+            else:
+                t = ops.tuned_tile(ops.CONV_FWD, x.dtype, 2 * x.N, x.H, x.W, x.C, y.C, op.k, op.stride, self.device, with_stats=True)
+            op._tiles[kind + "2"] = t
+        return t
+
+    def _base_conv(self, op, x, raw, y, res, stat, aff, nseg=1):
+        """Forward BaseConv on the given views — the op's own, or (nseg = 2) both frames of the shared per-frame network with
+        per-frame statistics: conv (+ sum / sum^2), then finalize and BN.SiLU apply (or the one launch for both).  The running
+        statistics are one batched launch at the end of the pass (the two frames' calls of a shared module update them in call
+        order there, whatever stream each frame ran on)."""
+        gamma, beta, eps, mom = self._bn_params(op)
+        t = self._tile(op, "fwd_stats", nseg)
+        w, wfrag = self._weights(op.mod, t)
+        scale, shift, mean, invstd = aff
+        ops.conv2d(x, w, raw, op.k, op.stride, stats=stat, tile=t, wfrag=wfrag, segments=nseg)
         if self.fused_finalize:
-            ops.bn_finalize_apply(u_sum, u_sq, a.y.pixels, gamma, beta, eps, scale, shift, mean, invstd, raw2, y2,
-                                  res=None if a.res is None else a.res.pair(), nseg=2)
+            ops.bn_finalize_apply(stat[0], stat[1], op.y.pixels, gamma, beta, eps, scale, shift, mean, invstd, raw, y, res=res,
+                                  nseg=nseg)
         else:
-            ops.bn_finalize(u_sum, u_sq, a.y.pixels, gamma, beta, eps, mom, None, None, scale, shift, mean, invstd,
-                            nseg=2)
-            ops.bn_silu_apply(raw2, scale, shift, y2, res=None if a.res is None else a.res.pair(), nseg=2)
+            ops.bn_finalize(stat[0], stat[1], op.y.pixels, gamma, beta, eps, mom, None, None, scale, shift, mean, invstd, nseg=nseg)
+            ops.bn_silu_apply(raw, scale, shift, y, res=res, nseg=nseg)
+
+    def _dgrad(self, op, dy, dx, acc, tile):
+        """Data gradient of the op's convolution: raw gradient `dy` -> gradient view `dx` of its input (accumulated at a fan-in)."""
+        w, wfrag = self._weights(op.mod, tile, transpose=True)
+        ops.conv2d(dy, w, dx, op.k, op.stride, mode=CONV_DGRAD, accumulate=acc, tile=tile, wfrag=wfrag)
 
     # ---- launch programs ------------------------------------------------------------------------------------
     # Step 1 runs the Python wrappers directly (kernel variants get tuned).  Step 2 runs them again under
@@ -800,9 +781,9 @@ class TrainPlan:
 
     def _run(self, name, body, key=None):
         from . import _lib
-        if self.force_serial or not self.tuned or self.device.type != "cuda" and not self.TAPE_ON_CPU:
+        if self.force_serial or not self.tuned:
             self._rec = None
-            body()                                               # direct (tuning step, profile(), CPU test runs)
+            body()                                               # direct (tuning step, profile())
             return
         prog = self.programs.get(name)
         if prog is None or prog[0] != key:
@@ -820,22 +801,19 @@ class TrainPlan:
     def _interpret(self, tape):
         """Replay a recorded pass: ONE library call walks the launches, stream switches and event pairs (csrc/tape.hip);
         Python is re-entered only for the recorded torch snippets and, in data-parallel runs, at the bucket marks."""
-        side, side2 = self.side, self.side2
-        extra = [self.side_w.get(k) for k in (3, 4, 5)]
+        side, side2, side3 = self.side, self.side2, self.side3         # all three or none (TrainPlan.__init__)
         if self.device.type == "cuda":
             main = torch.cuda.current_stream(self.device)
             main_h = C.c_void_p(main.cuda_stream)
             side_h = C.c_void_p(side.cuda_stream) if side is not None else None
-            more = [C.c_void_p(st_.cuda_stream) if st_ is not None else None for st_ in [side2] + extra]
-            while more and more[-1] is None:
-                more.pop()
+            more = [C.c_void_p(st_.cuda_stream) for st_ in (side2, side3) if st_ is not None]
             if torch.cuda.is_current_stream_capturing():
                 # hipGraph capture (TrainStep(graph=True)): forks across more than two streams segfault inside capture_end on
                 # this ROCm build — chain 2 folds back onto the main stream there (sy_tape_replay_n's fallback)
                 more = []
         else:
             main, main_h, side_h, more = None, C.c_void_p(0), None, []
-        chains = [main, side, side2] + extra
+        chains = [main, side, side2, side3]
 
         def snippet(fn, k):
             if k and chains[k] is not None:
@@ -845,28 +823,14 @@ class TrainPlan:
                 fn()
         on_bucket = None
         if self.on_bucket is not None:
-            on_bucket = lambda k: self.on_bucket(k, main, [s_ for s_ in [side, side2] + extra if s_ is not None])      # noqa: E731
+            on_bucket = lambda k: self.on_bucket(k, main, [s_ for s_ in chains[1:] if s_ is not None])      # noqa: E731
         tape.replay(main_h, side_h, snippet, on_bucket, more=more)
 
     def _forward_op(self, op):
         nch = 5 + self.nc
         k = op.kind
         if k == "conv":
-            gamma, beta, eps, mom = self._bn_params(op)
-            w = self.cache.conv_weight(op.mod)
-            t = op.tile("fwd_stats")
-            scale, shift, mean, invstd = op.aff
-            ops.conv2d(op.x, w, op.yraw, op.k, op.stride, stats=op.stat, tile=t,
-                       wfrag=self.cache.conv_weight_frag(op.mod) if t >= ops.TILE_WR else None)
-            # running statistics: one batched launch at the end of the pass (the two frames' calls of a shared
-            # module update them in call order there, whatever stream each frame ran on)
-            if self.fused_finalize:
-                ops.bn_finalize_apply(op.stat[0], op.stat[1], op.y.pixels, gamma, beta, eps, scale, shift, mean, invstd,
-                                      op.yraw, op.y, res=op.res)
-            else:
-                ops.bn_finalize(op.stat[0], op.stat[1], op.y.pixels, gamma, beta, eps, mom,
-                                None, None, scale, shift, mean, invstd)
-                ops.bn_silu_apply(op.yraw, scale, shift, op.y, res=op.res)
+            self._base_conv(op, op.x, op.yraw, op.y, op.res, op.stat, op.aff)
         elif k == "resize":
             ops.resize_nearest(op.src, op.dst)
         elif k == "spp":
@@ -928,7 +892,7 @@ class TrainPlan:
         workgroups busy for ~0.25 ms and nothing else can run beside it — the 60 us of memsets used to sit in front of the backward
         pass.  backward() (wait=True) orders its streams behind them, or clears the arenas itself when no loss call did (the
         sub-module plans, a caller that skips loss())."""
-        st = self.side_w.get(3) or self.side2 or self.side
+        st = self.side3
         if wait:
             if self._zeroed is None:
                 ops.zero(self.arena)
@@ -1002,9 +966,6 @@ class TrainPlan:
     def _backward_ops(self, d_raw):
         G = self.grads
         G.reset()
-        for op in self.ops:                                      # fused-reduce marks are per pass (set by the consumer's data gradient)
-            if op.kind == "conv":
-                op.bnr_by = None
         self.ring_i = 0
         self._split_j = 0                                        # layers issued by _conv_pair_backward_split in this pass
         nf = self.n_frame_ops
@@ -1017,7 +978,7 @@ class TrainPlan:
         self._bucket_marks(-1)                                   # ranges no kernel writes (unused parameters)
         split = self.bwd_split and nf > 0
         self._chain, self._wg_flip = 0, 0
-        head_chain = HEAD_BWD_CHAINS and self.head is not None and self.side2 is not None
+        head_chain = self.head is not None and self.side2 is not None
         n_head = len(self.ops) - self.n_head_start               # the backward walk starts with the head's ops, last level first
         if head_chain:
             self._mark("dep", (0, 2))                            # d_raw / dpad are ready on the main stream
@@ -1044,7 +1005,7 @@ class TrainPlan:
                     if split:
                         self._conv_pair_backward_split(a, b2)
                     else:
-                        self._conv_pair_backward(a, b2)
+                        self._conv_backward(a, b2)
                 else:
                     for op in (b2, a):
                         if split:
@@ -1058,27 +1019,27 @@ class TrainPlan:
         if split:
             self._mark("cur", 0)
             self._mark("dep", (2, 0))
-        for k in WGRAD_STREAMS:                                  # "join" covers stream 1; the further weight-gradient streams join
-            if k != 1:                                           # here: whoever reads the arena next does so on the main stream
-                self._mark("dep", (k, 0))
-        self._mark("join")
+        self._mark("dep", (WGRAD_STREAMS[1], 0))                 # "join" covers stream 1; the second weight-gradient stream joins
+        self._mark("join")                                       # here: whoever reads the arena next does so on the main stream
 
     # ---- weight gradients off the critical path -------------------------------------------------------------
     # Nothing downstream in the backward pass reads a weight gradient, so every wgrad (+ its fold) runs on the side
     # stream, ordered after the main-stream kernels that produced its raw gradient, and the main stream goes
     # straight on to the data gradient of the same layer.
-    def _scratch(self, numel):
-        """Next raw-gradient slot of the ring.  A slot's raw gradient has up to three readers: the weight gradient (on a
-        weight-gradient stream) and the data gradient(s) on the chain(s) that produced it; each marks "slot_done" on its own
-        stream behind its launch, and the chain that overwrites the slot next waits ("acquire_cur") for every one of those
-        events that lives on ANOTHER stream — several chains share the ring (head levels 1-2 / the support frame on chain 2),
-        so the next writer is not necessarily on the stream of the previous data gradient."""
+    def _scratch(self, numel, acquire=True):
+        """Next raw-gradient slot of the ring (self._slot; None with a buffer per layer, RING == 0).  A slot's raw gradient has up
+        to three readers: the weight gradient (on a weight-gradient stream) and the data gradient(s) on the chain(s) that produced
+        it; each marks "slot_done" on its own stream behind its launch, and the chain that overwrites the slot next waits
+        ("acquire_cur") for every one of those events that lives on ANOTHER stream — several chains share the ring (head levels
+        1-2 / the support frame on chain 2), so the next writer is not necessarily on the stream of the previous data gradient
+        (ADVICE r03).  acquire=False: the caller issues the waits itself (the split backward, per chain and in batches)."""
         if self.RING <= 0:
             self._slot = None
             return self._own_buffer(numel)
         self.ring_i = (self.ring_i + 1) % self.RING
         self._slot = self.ring_i
-        self._mark("acquire_cur", self._slot)
+        if acquire:
+            self._mark("acquire_cur", self._slot)
         return self.dyraw_ring[self._slot][:numel]
 
     def _own_buffer(self, numel):
@@ -1140,17 +1101,6 @@ class TrainPlan:
             ops.pred_grad_fold(d_raw, op.a0, hwk, nc, sc, cin, g_reg, g_obj, g_cls, gb_r, gb_o, gb_c, self.pred_ws)
         self._on_side(wg, stream=1)                                  # one scratch for the three levels: always stream 1
 
-    def _bn_backward(self, op, dyraw):
-        """Residual fan-in + BatchNorm/SiLU backward of one BaseConv call: fills `dyraw` (grad of the raw conv
-        output) and accumulates dgamma / dbeta."""
-        G = self.grads
-        gamma = self._bn_params(op)[0]
-        dgamma, dbeta = self._bn_grads(op)
-        dY = G.view(op.y)
-        dres, acc = (None, False) if op.res is None else G.target(op.res)    # y = silu(bn(conv)) + res: dres (+)= dY
-        scale, shift, mean, invstd = op.aff
-        self._bn_bwd(op, op.yraw, dY, (scale, shift, mean, invstd), gamma, op.bsum, dyraw, dgamma, dbeta, dres=dres, acc=acc)
-
     def _wgrad(self, op, x, dyraw):
         w = base_convs(op.mod)[0].conv.weight                        # stacked parts: their arena slots follow this one
         key = "wgrad%d" % x.N
@@ -1172,40 +1122,34 @@ class TrainPlan:
             kk = op.k * op.k
             ops.rows_add_f32(gw, sc, w.shape[0], w.shape[1] * kk, w.shape[1] * kk, x.C * kk, zero_src=True)
 
-    def _conv_pair_backward(self, a, b2):
-        """Layer i of the current-frame and support-frame networks together: per-frame BN backward (separate
-        statistics), then ONE wgrad and ONE dgrad launch over the 2B images (the weights are shared)."""
+    def _conv_backward(self, a, b2=None):
+        """One launch per pass of a BaseConv's backward: BatchNorm backward, weight gradient (on a side stream), data gradient.
+        b2 None: the op on its own views (fusion / head convs).  b2 = the support-frame twin of `a`: layer i of both per-frame
+        networks together over the paired views — per-frame BN backward (nseg 2, separate statistics), then ONE wgrad and ONE
+        dgrad launch over the 2B images (the weights are shared)."""
         G = self.grads
-        N, H, W, C = a.y.N, a.y.H, a.y.W, a.y.C
-        full = self._scratch(2 * N * H * W * C).view(2 * N, H, W, C)
+        nseg, both = (1, lambda v: v) if b2 is None else (2, View.pair)
+
+        def target(va, vb):                                          # gradient view of an input, both frames' halves as one
+            g, acc = G.target(va)
+            if b2 is not None:
+                gb, accb = G.target(vb)
+                assert acc == accb and g.root[0] is gb.root[0]
+            return both(g), acc
+        N, H, W, C = nseg * a.y.N, a.y.H, a.y.W, a.y.C
+        dy = View(self._scratch(N * H * W * C).view(N, H, W, C), N, H, W, C)
         slot = self._slot
-        dy2 = View(full, 2 * N, H, W, C)
         gamma = self._bn_params(a)[0]
         dgamma, dbeta = self._bn_grads(a)
-        dYa, dYb = G.view(a.y), G.view(b2.y)
-        assert dYa.root[0] is dYb.root[0]
-        dY2 = dYa.pair()
-        dres2, acca = None, False
-        if a.res is not None:                                        # y = silu(bn(conv)) + res, both frames at once
-            dra, acca = G.target(a.res)
-            drb, accb = G.target(b2.res)
-            assert acca == accb and dra.root[0] is drb.root[0]
-            dres2 = dra.pair()                                       # written by the BN backward apply pass below
-        _, _, u_bsum, (scale, shift, mean, invstd) = a.unit
-        raw2 = a.yraw.pair()
-        self._bn_bwd(a, raw2, dY2, (scale, shift, mean, invstd), gamma, u_bsum, dy2, dgamma, dbeta, nseg=2, dres=dres2, acc=acca)
-        self._on_side(lambda: self._wgrad(a, a.x.pair(), dy2), slot)
+        dY = both(G.view(a.y))
+        # y = silu(bn(conv)) + res: dres (+)= dY, written by the BN backward apply pass
+        dres, acc = (None, False) if a.res is None else target(a.res, b2 and b2.res)
+        raw, bsum, aff = (a.yraw, a.bsum, a.aff) if b2 is None else (a.yraw.pair(), a.unit[2], a.unit[3])
+        self._bn_bwd(a, raw, dY, aff, gamma, bsum, dy, dgamma, dbeta, nseg=nseg, dres=dres, acc=acc)
+        self._on_side(lambda: self._wgrad(a, both(a.x), dy), slot)
         if a.need_dx:
-            dxa, acca = G.target(a.x)
-            dxb, accb = G.target(b2.x)
-            assert acca == accb and dxa.root[0] is dxb.root[0]
-            t = a._tiles.get("dgrad2")
-            if t is None:
-                t = ops.tuned_tile(CONV_DGRAD, dy2.dtype, 2 * N, H, W, C, a.x.C, a.k, a.stride, self.device)
-                a._tiles["dgrad2"] = t
-            ops.conv2d(dy2, self.cache.conv_weight(a.mod, transpose=True), dxa.pair(), a.k, a.stride,
-                       mode=CONV_DGRAD, accumulate=acca, tile=t,
-                       wfrag=self.cache.conv_weight_frag(a.mod, transpose=True) if t >= ops.TILE_WR else None)
+            dx, acc = target(a.x, b2 and b2.x)
+            self._dgrad(a, dy, dx, acc, self._tile(a, "dgrad", nseg))
             if slot is not None:
                 self._mark("slot_done", slot)                        # ... and this chain's reader of the slot (see _scratch)
 
@@ -1215,12 +1159,8 @@ class TrainPlan:
         data gradient), the weight gradient ONCE over both frames on stream 1 behind both chains' raw gradients."""
         G = self.grads
         N, H, W, C = a.y.N, a.y.H, a.y.W, a.y.C
-        if self.RING <= 0:
-            slot, full = None, self._own_buffer(2 * N * H * W * C).view(2 * N, H, W, C)
-        else:
-            self.ring_i = (self.ring_i + 1) % self.RING
-            slot = self.ring_i
-            full = self.dyraw_ring[slot][:2 * N * H * W * C].view(2 * N, H, W, C)
+        full = self._scratch(2 * N * H * W * C, acquire=False).view(2 * N, H, W, C)
+        slot = self._slot
         dy2 = View(full, 2 * N, H, W, C)
         dys = (View(full[:N], N, H, W, C), View(full[N:], N, H, W, C))
         gamma = self._bn_params(a)[0]
@@ -1241,9 +1181,7 @@ class TrainPlan:
                 for m in range(min(K, len(WGRAD_STREAMS))):
                     self._mark("acquire_cur", (slot + K - 1 - m) % self.RING)
             dres, acc = (None, False) if op.res is None else G.target(op.res)
-            scale, shift, mean, invstd = op.aff
-            self._bn_bwd(op, op.yraw, G.view(op.y), (scale, shift, mean, invstd), gamma, op.bsum, dyr, dgamma, dbeta,
-                         dres=dres, acc=acc, atomic=True)
+            self._bn_bwd(op, op.yraw, G.view(op.y), op.aff, gamma, op.bsum, dyr, dgamma, dbeta, dres=dres, acc=acc, atomic=True)
         self._chain = 0
         self._on_side(lambda: self._wgrad(a, a.x.pair(), dy2), slot, chains=(0, 2))
         if a.need_dx:
@@ -1251,32 +1189,10 @@ class TrainPlan:
             for k, (op, dyr) in enumerate(zip((a, b2), dys)):
                 self._mark("cur", 2 * k)
                 dx, acc = G.target(op.x)
-                pre = self._bnr_producer(op, dx, acc, t)
-                if pre is not None:                                  # ... + the BatchNorm-backward reduce of the layer that made op.x
-                    pre.bnr_by = op
-                ops.conv2d(dyr, self.cache.conv_weight(a.mod, transpose=True), dx, a.k, a.stride, mode=CONV_DGRAD,
-                           accumulate=acc, tile=t,
-                           wfrag=self.cache.conv_weight_frag(a.mod, transpose=True) if t >= ops.TILE_WR else None,
-                           bn_reduce=None if pre is None else (pre.yraw, pre.aff[0], pre.aff[1], pre.bsum))
+                self._dgrad(a, dyr, dx, acc, t)
                 if CHAIN_SLOT_DONE and slot is not None:
                     self._mark("slot_done", slot)                    # this chain's reader of its half of the slot
         self._mark("cur", 0)
-
-    def _conv_backward(self, op):
-        G = self.grads
-        C = op.y.C
-        dyraw = View(self._scratch(op.y.pixels * C).view(op.y.N, op.y.H, op.y.W, C), op.y.N, op.y.H, op.y.W, C)
-        slot = self._slot
-        self._bn_backward(op, dyraw)
-        self._on_side(lambda: self._wgrad(op, op.x, dyraw), slot)
-        if op.need_dx:
-            dx, acc = G.target(op.x)
-            t = op.tile("dgrad")
-            ops.conv2d(dyraw, self.cache.conv_weight(op.mod, transpose=True), dx, op.k, op.stride,
-                       mode=CONV_DGRAD, accumulate=acc, tile=t,
-                       wfrag=self.cache.conv_weight_frag(op.mod, transpose=True) if t >= ops.TILE_WR else None)
-            if slot is not None:
-                self._mark("slot_done", slot)                        # ... and this chain's reader of the slot (see _scratch)
 
     # ------------------------------------------------------------------------------------------------
     def profile(self, x, targets, iters=2, detail=False):
@@ -1346,10 +1262,12 @@ def get_train_plan(model, x):
 
 
 class _Pin:
-    """One count of a plan's `pending`, given back exactly once — by release() or when the holder (an autograd node's ctx) dies."""
+    """One count of a plan's `pending` (the plan cache never evicts — releases — a pinned plan), taken here and given back exactly
+    once: by release() or when the holder (an autograd node's ctx, a TrainStep) dies."""
 
     def __init__(self, plan):
         self.plan = plan
+        plan.pending += 1
 
     def release(self):
         if self.plan is not None:
@@ -1360,6 +1278,26 @@ class _Pin:
         self.release()
 
 
+def _pin(ctx, plan):
+    """An autograd node pins its plan until its backward runs OR the node is dropped without one; not under no_grad (no input
+    needs a gradient: no backward will come)."""
+    ctx.plan = plan
+    ctx.pin = _Pin(plan) if any(ctx.needs_input_grad) else None
+
+
+def _unpin(ctx):
+    if ctx.pin is not None:
+        ctx.pin.release()
+    return ctx.plan
+
+
+def _loss_outputs(ctx, out):
+    """Loss dict of plan.loss -> (total, stats) as the outputs of an autograd node (stats: no gradient)."""
+    stats = torch.stack([out[k] for k in ("iou_loss", "l1_loss", "conf_loss", "cls_loss", "num_fg")]).clone()
+    ctx.mark_non_differentiable(stats)
+    return out["total_loss"].clone(), stats
+
+
 class _PlanFunction(torch.autograd.Function):
     """total_loss = TAL(plan.forward(x)); the forward pass also produces d(total)/d(raw) (closed form in
     sy_tal_loss), so backward only scales it by the incoming gradient (GradScaler's loss scale) and
@@ -1368,24 +1306,14 @@ class _PlanFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, x, labels, support, *params):
-        ctx.plan = plan
-        ctx.counted = any(ctx.needs_input_grad)         # False under no_grad: no backward will come
-        if ctx.counted:
-            plan.pending += 1              # the plan cache must not evict (release) it before this node's backward ran
-            ctx.pin = _Pin(plan)           # ... and is released when backward runs OR the node is dropped without one
+        _pin(ctx, plan)
         plan.forward(x)
-        out, d_raw = plan.loss(labels, support)
-        ctx.d_raw = d_raw
-        stats = torch.stack([out[k] for k in ("iou_loss", "l1_loss", "conf_loss", "cls_loss", "num_fg")]).clone()
-        ctx.mark_non_differentiable(stats)
-        return out["total_loss"].clone(), stats
+        out, ctx.d_raw = plan.loss(labels, support)
+        return _loss_outputs(ctx, out)
 
     @staticmethod
     def backward(ctx, g_total, _g_stats):
-        plan = ctx.plan
-        if ctx.counted:
-            ctx.pin.release()
-            ctx.counted = False
+        plan = _unpin(ctx)
         arena = plan.backward((ctx.d_raw * g_total.float()).contiguous()).clone()
         return (None, None, None, None) + _arena_views(arena, plan.params)
 
@@ -1409,20 +1337,12 @@ class _BackboneFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, x, *params):
-        ctx.plan = plan
-        ctx.counted = any(ctx.needs_input_grad)         # False under no_grad: no backward will come
-        if ctx.counted:
-            plan.pending += 1
-            ctx.pin = _Pin(plan)
-        fused = plan.forward(x)
-        return tuple(f.export() for f in fused)
+        _pin(ctx, plan)
+        return tuple(f.export() for f in plan.forward(x))
 
     @staticmethod
     def backward(ctx, *gouts):
-        plan = ctx.plan
-        if ctx.counted:
-            ctx.pin.release()
-            ctx.counted = False
+        plan = _unpin(ctx)
         arena = plan.backward(None, d_fused=[g.float() for g in gouts]).clone()
         return (None, None) + _arena_views(arena, plan.params)
 
@@ -1433,24 +1353,14 @@ class _HeadFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, labels, support, f0, f1, f2, *params):
-        ctx.plan = plan
-        ctx.counted = any(ctx.needs_input_grad)
-        if ctx.counted:
-            plan.pending += 1
-            ctx.pin = _Pin(plan)
+        _pin(ctx, plan)
         plan.forward((f0, f1, f2))
-        out, d_raw = plan.loss(labels, support)
-        ctx.d_raw = d_raw
-        stats = torch.stack([out[k] for k in ("iou_loss", "l1_loss", "conf_loss", "cls_loss", "num_fg")]).clone()
-        ctx.mark_non_differentiable(stats)
-        return out["total_loss"].clone(), stats
+        out, ctx.d_raw = plan.loss(labels, support)
+        return _loss_outputs(ctx, out)
 
     @staticmethod
     def backward(ctx, g_total, _g_stats):
-        plan = ctx.plan
-        if ctx.counted:
-            ctx.pin.release()
-            ctx.counted = False
+        plan = _unpin(ctx)
         arena = plan.backward((ctx.d_raw * g_total.float()).contiguous()).clone()
         gf = tuple(g.to(plan.tdtype) for g in plan.fused_grads())
         return (None, None, None) + gf + _arena_views(arena, plan.params)
@@ -1477,21 +1387,15 @@ def head_train_forward(head, xin, labels):
     key = ("train-head", int(x0.shape[0]), shapes, dt, str(x0.device))
     plan = head._plans.get(key, lambda: TrainPlan(head, int(x0.shape[0]), 0, 0, dt, x0.device, parts="head", feat_shapes=shapes,
                                                   pool=head._plans))
-    lab, sup = split_targets_head(head, labels)
+    lab, sup = split_targets(head, labels)
     total, stats = _HeadFunction.apply(plan, lab, sup, xin[0], xin[1], xin[2], *plan.params)
     return total, stats[0], stats[2], stats[3], stats[1], stats[4]
 
 
-def split_targets_head(head, targets):
-    if getattr(head, "single_labels", False) and torch.is_tensor(targets):
-        return targets, targets
-    return targets
-
-
-def split_targets(model, targets):
+def split_targets(head, targets):
     """(labels, support): TALHead takes the pair `(t, st)` (yolox.py:37-38, tal_head.py:280-286); PIPEHead one tensor,
     which then serves as its own support (model/pipe_head.py)."""
-    if getattr(model.head, "single_labels", False) and torch.is_tensor(targets):
+    if getattr(head, "single_labels", False) and torch.is_tensor(targets):
         return targets, targets
     labels, support = targets
     return labels, support
@@ -1503,7 +1407,7 @@ def train_forward(model, x, targets):
         x = x.paired_with_self() if isinstance(x, FramePairsU8) else torch.cat([x, x], dim=1)
     assert x.size()[1] == 6
     plan = get_train_plan(model, x)
-    labels, support = split_targets(model, targets)
+    labels, support = split_targets(model.head, targets)
     total, stats = _PlanFunction.apply(plan, x, labels, support, *plan.params)
     return {"total_loss": total, "iou_loss": stats[0], "l1_loss": stats[1], "conf_loss": stats[2],
             "cls_loss": stats[3], "num_fg": stats[4]}
@@ -1524,7 +1428,7 @@ class TrainStep:
         self._comm16 = None                         # bf16 mirror of the arena (grad_comm_dtype="bf16")
         self._t_bwd_end, self._t_comm_end = None, None
         self.exposed_allreduce_ms = None            # of the last step: all-reduce time NOT hidden behind backward
-        self.plan = None
+        self.plan, self._pin = None, None           # the plan of the current input size and this step's hold on it (_ensure)
         # optional hipGraph replay of forward + loss + backward (STREAMYOLO_GRAPH=1 / graph=True).  Off by default:
         # on ROCm 7 replaying this ~1500-node graph costs MORE host time than the launch tapes (measured)
         self.use_graph = (os.environ.get("STREAMYOLO_GRAPH", "0") != "0") if graph is None else bool(graph)
@@ -1540,8 +1444,8 @@ class TrainStep:
     def close(self):
         """Release the step's pin on its plan (`pending`): the plan cache may evict it again.  Called by __del__; idempotent."""
         if getattr(self, "plan", None) is not None:
-            self.plan.pending = max(0, self.plan.pending - 1)
-            self.plan = None
+            self._pin.release()
+            self.plan = self._pin = None
 
     def __del__(self):
         try:
@@ -1555,10 +1459,8 @@ class TrainStep:
         other sizes, a second TrainStep — cannot evict and release it under this one."""
         plan = get_train_plan(self.model, x)
         if plan is not self.plan:
-            if self.plan is not None:
-                self.plan.pending = max(0, self.plan.pending - 1)
-            plan.pending += 1
-            self.plan = plan
+            self.close()
+            self.plan, self._pin = plan, _Pin(plan)
             for p in plan.params:
                 p.grad = plan.gview[id(p)]
         return plan
@@ -1591,7 +1493,7 @@ class TrainStep:
             scaler = None
         plan = self._ensure(x)
         self._last = (x, targets)
-        lab, sup = split_targets(self.model, targets)
+        lab, sup = split_targets(self.model.head, targets)
         self._works, self._reduced = [], set()
         plan.on_bucket = self._reduce_bucket if (self.world > 1 and not self.use_graph) else None
         graphable = self.use_graph and x.is_cuda and plan.run_table is not None and plan.tuned
@@ -1618,7 +1520,7 @@ class TrainStep:
                 if self._t_bwd_end is None:
                     self._t_bwd_end, self._t_comm_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 self._t_bwd_end.record()                        # backward (all chains joined) is complete here on the main stream
-            t_host = __import__("time").perf_counter()
+            t_host = time.perf_counter()
             for k in range(len(plan.buckets)):
                 if k not in self._reduced:
                     self._reduce_bucket(k, None, None)
@@ -1633,7 +1535,7 @@ class TrainStep:
                 self._t_comm_end.record()
                 self._exposed_pending = True                    # read lazily (exposed_allreduce): no synchronisation in the step
             else:
-                self.exposed_allreduce_ms = (__import__("time").perf_counter() - t_host) * 1e3
+                self.exposed_allreduce_ms = (time.perf_counter() - t_host) * 1e3
         return out
 
     def exposed_allreduce(self):
