@@ -298,6 +298,40 @@ SY_API int sy_postprocess(const float* pred, int B, int A, int num_classes, floa
                    int max_det, float* out_det, int32_t* out_index, int32_t* out_count,
                    void* workspace, void* stream);
 
+/* sy_postprocess with a policy PER BATCH ROW: what counts as a detection is table data, read on the device, so one recorded
+ * launch list serves cameras with different thresholds, class lists, NMS modes and output caps.  `rows`: B records in DEVICE
+ * memory.  Everything else is as in sy_postprocess (same workspace, same output layout: out_det [B, max_det, 7], out_index
+ * [B, max_det], out_count [B]).  Per row b:
+ *   1. candidates   the anchors with obj * max_c cls >= conf_thre whose arg-max class (first maximum wins) has its bit set in
+ *                   class_mask.  A masked-out anchor is gone BEFORE the NMS: it suppresses nothing, in either mode.
+ *   2. order        score descending, ties by ascending anchor index (the 64-bit sort key of sy_postprocess).  With
+ *                   max_candidates = k > 0 only the first k entries of that order remain.
+ *   3. class-aware  (flags bit 0 clear) exactly what sy_postprocess returns for a prediction tensor that holds only the
+ *                   remaining candidates' anchors: the class offset unit max_coord + 1 is taken over the REMAINING candidates
+ *                   (with a cut: a second reduction behind the sort), not over everything that passed the confidence filter.
+ *   4. agnostic     (flags bit 0 set) the same walk with offset 0 — torchvision.ops.nms on the raw corner boxes, as
+ *                   yolox.utils.postprocess(class_agnostic=True) calls it.  The output rows still carry the arg-max class and
+ *                   its class_conf.
+ *   5. max_det      the output is the first max_det rows of the uncapped kept list; out_count = min(kept, max_det).  The serial
+ *                   walk stops as soon as that many boxes survive (later chunks could only append).  Entries of out_det /
+ *                   out_index past out_count are unspecified.
+ *   6. default row  {the thresholds, flags 0, both caps 0, every class bit set} gives, bit for bit, det / index / count of
+ *                   sy_postprocess with those thresholds.  An all-zero record (no class bit) gives count 0.
+ * SY_ERR_UNSUPPORTED for num_classes > 128 and, as sy_postprocess, for A above the LDS sort limit (16384). */
+typedef struct sy_det_policy {      /* 40 bytes, one per batch row, DEVICE memory */
+    float    conf_thre;             /* candidate iff obj * class_conf >= conf_thre */
+    float    nms_thre;              /* a later box is suppressed iff IoU > nms_thre with an earlier kept box */
+    int32_t  flags;                 /* bit 0: class-agnostic NMS (no per-class coordinate offset) */
+    int32_t  max_candidates;        /* > 0: only the best max_candidates candidates enter the NMS; 0: all */
+    int32_t  max_det;               /* > 0: at most this many detections are written (clamped to the launch's max_det); 0: the launch's */
+    int32_t  reserved;              /* 0 */
+    uint32_t class_mask[4];         /* bit c % 32 of word c / 32: class c is reported (num_classes <= 128) */
+} sy_det_policy;
+#define SY_DET_AGNOSTIC 1
+SY_API int sy_postprocess_rows(const float* pred, int B, int A, int num_classes, const sy_det_policy* rows,
+                               int max_det, float* out_det, int32_t* out_index, int32_t* out_count,
+                               void* workspace, void* stream);
+
 /* Optimizer + EMA step of one training iteration in one launch.  Replaces
  * `scaler.step(optimizer)` + `ema_model.update(model)` (exps/train_utils/double_trainer.py:115-119):
  * torch.optim.SGD(momentum, nesterov=True) semantics per entry — d = g*grad_scale; d += weight_decay*p;

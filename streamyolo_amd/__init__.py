@@ -11,13 +11,13 @@ from .model.dfp_pafpn import DFPPAFPN
 from .model.pipe_head import PIPEHead
 from .model.tal_head import TALHead
 from .model.yolox import YOLOX
-from .postprocess import postprocess
+from .postprocess import DetectionPolicy, postprocess
 from .data import Surface
 from .streaming import MultiStreamDetector, StreamingDetector, TrackConfig
 from .scoring import DetectionScorer, score_coco
 
 __all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model", "DeviceGradScaler",
-           "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig", "DetectionScorer", "score_coco"]
+           "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig", "DetectionPolicy", "DetectionScorer", "score_coco"]
 __version__ = "0.1.0"
 
 MODEL_ZOO = {

@@ -104,6 +104,16 @@ class StreamLevel(C.Structure):
                 ("C", C.c_int32), ("ld", C.c_int32)]
 
 
+class DetPolicy(C.Structure):
+    """sy_det_policy (include/streamyolo_hip.h): 40 bytes of DEVICE memory per batch row."""
+    _fields_ = [("conf_thre", C.c_float), ("nms_thre", C.c_float), ("flags", C.c_int32), ("max_candidates", C.c_int32),
+                ("max_det", C.c_int32), ("reserved", C.c_int32), ("class_mask", C.c_uint32 * 4)]
+
+
+DET_AGNOSTIC = 1                               # SY_DET_AGNOSTIC
+DET_MAX_CLASSES = 128                          # bits of sy_det_policy.class_mask
+
+
 class TrackTick(C.Structure):
     """sy_track_tick (include/streamyolo_hip.h): 32 bytes of DEVICE memory per batch row."""
     _fields_ = [("dt_frames", C.c_int32), ("horizon", C.c_float), ("img_w", C.c_float), ("img_h", C.c_float),
@@ -182,6 +192,7 @@ SIGNATURES = {
     "sy_postprocess_workspace_bytes": (_L, [_I, _I]),
     "sy_head_decode": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
     "sy_postprocess": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "sy_postprocess_rows": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "sy_sgd_ema_step": (_I, [_P, _I, _I, _F, _F, _F, _F, _I, _P]),
     "sy_grad_nonfinite": (_I, [_P, _I, _I, _P, _P]),
     "sy_sgd_ema_step_scaled": (_I, [_P, _I, _I, _F, _F, _F, _F, _P, _P]),

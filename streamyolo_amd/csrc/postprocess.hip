@@ -262,6 +262,247 @@ __global__ __launch_bounds__(kSweepThreads) void nms_sweep_kernel(const float* p
     }
 }
 
+// ---- sy_postprocess_rows: the same three kernels with a policy record per batch row (sy_det_policy, device memory) ----------------
+// Kernels of their own: callers without a policy table keep issuing exactly the launches above.  Structure, arithmetic and its
+// order are those of the kernels above; what differs is marked "policy:".
+__global__ __launch_bounds__(kRankThreads) void nms_rank_rows_kernel(const float* pred, int A, int nc, const sy_det_policy* rows,
+                                                                     unsigned char* ws, PostLayout L, int sort_n) {
+    SY_DYN_SMEM(smem);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem);        // [sort_n]
+    float* s_max = reinterpret_cast<float*>(smem + (size_t)sort_n * 8);           // [kRankThreads/64]
+    int& s_count = *reinterpret_cast<int*>(smem + (size_t)sort_n * 8 + (kRankThreads / 64) * 4);
+    const int img = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* P = pred + (long long)img * A * (5 + nc);
+    unsigned char* wsi = ws + (long long)img * L.image_bytes;
+    float* rec = reinterpret_cast<float*>(wsi + L.rec_off);
+    int* count_out = reinterpret_cast<int*>(wsi + L.count_off);
+    // policy: the row's record, the same words in every thread (ordinary loads)
+    const sy_det_policy* pol = rows + img;
+    const float conf_thre = pol->conf_thre;
+    const bool agnostic = (pol->flags & SY_DET_AGNOSTIC) != 0;
+    const int max_cand = pol->max_candidates;
+    const unsigned cm0 = pol->class_mask[0], cm1 = pol->class_mask[1], cm2 = pol->class_mask[2], cm3 = pol->class_mask[3];
+
+    if (tid == 0) s_count = 0;
+    for (int i = tid; i < sort_n; i += kRankThreads) keys[i] = ~0ull;
+    __syncthreads();
+
+    float lmax = -INFINITY;
+    for (int a = tid; a < A; a += kRankThreads) {
+        const float* r = P + (long long)a * (5 + nc);
+        float best = r[5];
+        int bc = 0;
+        for (int c = 1; c < nc; ++c) { const float v = r[5 + c]; if (v > best) { best = v; bc = c; } }
+        const float score = r[4] * best;
+        const unsigned word = bc < 32 ? cm0 : (bc < 64 ? cm1 : (bc < 96 ? cm2 : cm3));       // policy: the arg-max class is reported
+        if (score >= conf_thre && ((word >> (bc & 31)) & 1u)) {
+            const int slot = atomicAdd(&s_count, 1);
+            const unsigned bits = __builtin_bit_cast(unsigned, score);
+            keys[slot] = ((unsigned long long)(0xffffffffu - bits) << 32) | (unsigned)a;
+            const float hw = r[2] / 2, hh = r[3] / 2;
+            const float x1 = r[0] - hw, y1 = r[1] - hh, x2 = r[0] + hw, y2 = r[1] + hh;
+            lmax = fmaxf(fmaxf(fmaxf(lmax, x1), fmaxf(y1, x2)), y2);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off));
+    if ((tid & 63) == 0) s_max[tid >> 6] = lmax;
+    __syncthreads();
+    int count = s_count;
+    float max_coord = s_max[0];
+    for (int w = 1; w < kRankThreads / 64; ++w) max_coord = fmaxf(max_coord, s_max[w]);
+
+    // bitonic sort (ascending) of the first `n2` keys; empty slots hold ~0 and sink to the end
+    int n2 = 1;
+    while (n2 < count) n2 <<= 1;
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < n2; i += kRankThreads) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const unsigned long long a = keys[i], b = keys[ixj];
+                    const bool up = ((i & k) == 0);
+                    if ((a > b) == up) { keys[i] = b; keys[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // policy: the cut.  The offset unit is the maximum over what REMAINS: with a cut, a second reduction over the sorted prefix
+    // (a maximum does not depend on the order it is taken in); the branch is uniform over the workgroup.
+    if (max_cand > 0 && count > max_cand) {
+        count = max_cand;
+        if (!agnostic) {
+            lmax = -INFINITY;
+            for (int i = tid; i < count; i += kRankThreads) {
+                const float* r = P + (long long)(keys[i] & 0xffffffffu) * (5 + nc);
+                const float hw = r[2] / 2, hh = r[3] / 2;
+                const float x1 = r[0] - hw, y1 = r[1] - hh, x2 = r[0] + hw, y2 = r[1] + hh;
+                lmax = fmaxf(fmaxf(fmaxf(lmax, x1), fmaxf(y1, x2)), y2);
+            }
+            for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off));
+            __syncthreads();                                   // (every thread has read the first reduction's s_max)
+            if ((tid & 63) == 0) s_max[tid >> 6] = lmax;
+            __syncthreads();
+            max_coord = s_max[0];
+            for (int w = 1; w < kRankThreads / 64; ++w) max_coord = fmaxf(max_coord, s_max[w]);
+        }
+    }
+
+    const float off_unit = max_coord + 1.0f;
+    for (int i = tid; i < count; i += kRankThreads) {
+        const int a = (int)(keys[i] & 0xffffffffu);
+        const float* r = P + (long long)a * (5 + nc);
+        float best = r[5];
+        int bc = 0;
+        for (int c = 1; c < nc; ++c) { const float v = r[5 + c]; if (v > best) { best = v; bc = c; } }
+        const float hw = r[2] / 2, hh = r[3] / 2;
+        float x1 = r[0] - hw, y1 = r[1] - hh, x2 = r[0] + hw, y2 = r[1] + hh;
+        if (!agnostic) {                                       // policy: agnostic = the raw corner boxes
+            const float off = (float)bc * off_unit;
+            x1 = x1 + off; y1 = y1 + off; x2 = x2 + off; y2 = y2 + off;
+        }
+        float* o = rec + (long long)i * kRec;
+        o[0] = x1; o[1] = y1; o[2] = x2; o[3] = y2;
+        o[4] = (x2 - x1) * (y2 - y1);
+        o[5] = __builtin_bit_cast(float, a);
+        o[6] = 0.0f; o[7] = 0.0f;
+    }
+    if (tid == 0) *count_out = count;
+}
+
+__global__ __launch_bounds__(64) void nms_mask_rows_kernel(unsigned char* ws, PostLayout L, const sy_det_policy* rows) {
+    const int img = blockIdx.y;
+    unsigned char* wsi = ws + (long long)img * L.image_bytes;
+    const float* rec = reinterpret_cast<const float*>(wsi + L.rec_off);
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(wsi + L.mask_off);
+    const int count = *reinterpret_cast<const int*>(wsi + L.count_off);
+    const float thr = rows[img].nms_thre;                      // policy: the row's threshold
+    const int nblk = (count + 63) / 64;
+    const long long ntiles = (long long)nblk * (nblk + 1) / 2;
+    __shared__ float cbox[64 * 5];
+    const int lane = threadIdx.x;
+    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        int rb = 0;
+        long long rem = t;
+        while (rem >= nblk - rb) { rem -= nblk - rb; ++rb; }
+        const int cb = rb + (int)rem;
+        const int j0 = cb * 64;
+        __syncthreads();
+        if (j0 + lane < count) {
+            const float* r = rec + (long long)(j0 + lane) * kRec;
+            cbox[lane * 5 + 0] = r[0]; cbox[lane * 5 + 1] = r[1]; cbox[lane * 5 + 2] = r[2];
+            cbox[lane * 5 + 3] = r[3]; cbox[lane * 5 + 4] = r[4];
+        }
+        __syncthreads();
+        const int i = rb * 64 + lane;
+        if (i < count) {
+            const float* r = rec + (long long)i * kRec;
+            const float x1 = r[0], y1 = r[1], x2 = r[2], y2 = r[3], ai = r[4];
+            unsigned long long bits = 0ull;
+            const int jn = (count - j0) < 64 ? (count - j0) : 64;
+            for (int jj = 0; jj < jn; ++jj) {
+                if (j0 + jj <= i) continue;
+                const float lx = fmaxf(x1, cbox[jj * 5 + 0]), ly = fmaxf(y1, cbox[jj * 5 + 1]);
+                const float rx = fminf(x2, cbox[jj * 5 + 2]), ry = fminf(y2, cbox[jj * 5 + 3]);
+                const float w = fmaxf(rx - lx, 0.0f), h = fmaxf(ry - ly, 0.0f);
+                const float inter = w * h;
+                const float iou = inter / (ai + cbox[jj * 5 + 4] - inter);
+                if (iou > thr) bits |= (1ull << jj);
+            }
+            mask[(long long)i * L.words + cb] = bits;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kSweepThreads) void nms_sweep_rows_kernel(const float* pred, int A, int nc, unsigned char* ws,
+                                                                       PostLayout L, const sy_det_policy* rows, int max_det,
+                                                                       float* out_det, int* out_index, int* out_count) {
+    SY_DYN_SMEM(smem);
+    unsigned long long* removed = reinterpret_cast<unsigned long long*>(smem);     // [L.words] suppressed-so-far bitmap
+    unsigned long long* kept = removed + L.words;                                   // [L.words] survivors of every chunk
+    int* base = reinterpret_cast<int*>(kept + L.words);                             // [L.words] survivors before the chunk
+    const int img = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const bool wave0 = tid < 64;
+    unsigned char* wsi = ws + (long long)img * L.image_bytes;
+    const float* rec = reinterpret_cast<const float*>(wsi + L.rec_off);
+    const unsigned long long* mask = reinterpret_cast<const unsigned long long*>(wsi + L.mask_off);
+    const int count = *reinterpret_cast<const int*>(wsi + L.count_off);
+    const int nblk = (count + 63) / 64;
+    const float* P = pred + (long long)img * A * (5 + nc);
+    float* det = out_det + (long long)img * max_det * 7;
+    int* oidx = out_index + (long long)img * max_det;
+    // policy: the row's cap on the detections written, never above the launch's (the output rows are max_det long)
+    const int row_cap = rows[img].max_det;
+    const int cap = sy_uniform((row_cap > 0 && row_cap < max_det) ? row_cap : max_det);
+
+    for (int w = tid; w < nblk; w += kSweepThreads) removed[w] = 0ull;
+    unsigned long long diag_next = (wave0 && lane < count) ? mask[(long long)lane * L.words] : 0ull;
+    __syncthreads();
+    int nwalk = nblk;                                                  // chunks walked: kept[k] is written for k < nwalk only
+    int total = 0;                                                     // survivors so far (from kept[]: the same in every thread)
+    for (int k = 0; k < nblk; ++k) {
+        if (wave0) {
+            const unsigned long long diag = diag_next;
+            const int in = (k + 1) * 64 + lane;
+            diag_next = (k + 1 < nblk && in < count) ? mask[(long long)in * L.words + k + 1] : 0ull;
+            unsigned long long rem = sy_uniform64(removed[k]);
+            unsigned long long alive = 0ull;
+            const int nl = sy_uniform((count - k * 64) < 64 ? (count - k * 64) : 64);
+            for (int l = 0; l < nl; ++l) {
+                const unsigned long long row = sy_readlane64(diag, l);
+                if (!((rem >> l) & 1ull)) { alive |= (1ull << l); rem |= row; }
+            }
+            if (lane == 0) kept[k] = alive;
+        }
+        __syncthreads();
+        const unsigned long long alive = kept[k];
+        // policy: the cap is reached — later chunks could only append rows that are not written.  Uniform over the workgroup.
+        total += __popcll(alive);
+        if (total >= cap) { nwalk = k + 1; break; }
+        const int w = k + 1 + tid;
+        if (alive != 0ull && w < nblk) {
+            const unsigned long long* col = mask + (long long)(k * 64) * L.words + w;
+            unsigned long long v[64];
+#pragma unroll
+            for (int j = 0; j < 64; ++j) v[j] = col[(long long)j * L.words];
+            unsigned long long acc = removed[w];
+#pragma unroll
+            for (int j = 0; j < 64; ++j)
+                if ((alive >> j) & 1ull) acc |= v[j];
+            removed[w] = acc;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int n = 0;
+        for (int k = 0; k < nwalk; ++k) { base[k] = n; n += __popcll(kept[k]); }
+        out_count[img] = n < cap ? n : cap;
+    }
+    __syncthreads();
+    const int nbox = count < nwalk * 64 ? count : nwalk * 64;
+    for (int i = tid; i < nbox; i += kSweepThreads) {
+        const int k = i >> 6, b = i & 63;
+        const unsigned long long alive = kept[k];
+        if (!((alive >> b) & 1ull)) continue;
+        const int pos = base[k] + __popcll(alive & ((1ull << b) - 1ull));
+        if (pos >= cap) continue;
+        const int a = __builtin_bit_cast(int, rec[(long long)i * kRec + 5]);
+        const float* r = P + (long long)a * (5 + nc);
+        float best = r[5];
+        int bc = 0;
+        for (int c = 1; c < nc; ++c) { const float v = r[5 + c]; if (v > best) { best = v; bc = c; } }
+        const float hw = r[2] / 2, hh = r[3] / 2;
+        float* d = det + (long long)pos * 7;
+        d[0] = r[0] - hw; d[1] = r[1] - hh; d[2] = r[0] + hw; d[3] = r[1] + hh;
+        d[4] = r[4]; d[5] = best; d[6] = (float)bc;
+        oidx[pos] = a;
+    }
+}
+
 // ---- sy_head_decode: the head's box decode / objectness sigmoid as a stand-alone pass over [B, A, 5+nc] -------------------------
 struct DecodeLevels {
     int n;
@@ -345,5 +586,34 @@ extern "C" int sy_postprocess(const float* pred, int B, int A, int num_classes, 
     if (SY_LAUNCH_OK() != 0) return SY_ERR_LAUNCH;
     SY_LAUNCH(nms_sweep_kernel, dim3(B), dim3(kSweepThreads), (size_t)L.words * 20, stream, pred, A, num_classes,
               (unsigned char*)workspace, L, max_det, out_det, out_index, out_count);
+    return SY_LAUNCH_OK() == 0 ? SY_OK : SY_ERR_LAUNCH;
+}
+
+extern "C" int sy_postprocess_rows(const float* pred, int B, int A, int num_classes, const sy_det_policy* rows, int max_det,
+                                   float* out_det, int32_t* out_index, int32_t* out_count, void* workspace, void* stream) {
+    if (pred == nullptr || rows == nullptr || out_det == nullptr || out_index == nullptr || out_count == nullptr ||
+        workspace == nullptr)
+        return SY_ERR_ARG;
+    if (B <= 0 || A <= 0 || num_classes <= 0 || max_det <= 0) return SY_ERR_ARG;
+    if (num_classes > 128) return SY_ERR_UNSUPPORTED;        // class_mask holds 128 bits
+    const int sort_n = next_pow2(A);
+    if (sort_n > 16384) return SY_ERR_UNSUPPORTED;          // as sy_postprocess
+    PostLayout L = make_layout(A);
+    const size_t rank_smem = (size_t)sort_n * 8 + 128;
+#ifndef SY_EMU
+    static sy_dev_once attr_done;
+    if (attr_done.need()) {
+        if (hipFuncSetAttribute((const void*)nms_rank_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 8 + 128) != hipSuccess)
+            return SY_ERR_LAUNCH;
+        attr_done.mark();
+    }
+#endif
+    SY_LAUNCH(nms_rank_rows_kernel, dim3(B), dim3(kRankThreads), rank_smem, stream, pred, A, num_classes, rows,
+              (unsigned char*)workspace, L, sort_n);
+    if (SY_LAUNCH_OK() != 0) return SY_ERR_LAUNCH;
+    SY_LAUNCH(nms_mask_rows_kernel, dim3(512, B), dim3(64), 0, stream, (unsigned char*)workspace, L, rows);
+    if (SY_LAUNCH_OK() != 0) return SY_ERR_LAUNCH;
+    SY_LAUNCH(nms_sweep_rows_kernel, dim3(B), dim3(kSweepThreads), (size_t)L.words * 20, stream, pred, A, num_classes,
+              (unsigned char*)workspace, L, rows, max_det, out_det, out_index, out_count);
     return SY_LAUNCH_OK() == 0 ? SY_OK : SY_ERR_LAUNCH;
 }

@@ -936,6 +936,57 @@ class TrackSlots:
                                   self.forecast_cnt)
 
 
+class PolicyTable:
+    """The per-row detection policies of a batched tick (ops.postprocess_rows): `table`, B sy_det_policy records in device memory,
+    with a ring of pinned host mirrors and ONE non-blocking upload() (the mechanism of StreamSlots).  A row that is not set holds
+    the all-zero record: no class is reported, its count is 0."""
+
+    def __init__(self, B, device):
+        import numpy as np
+        from . import _lib
+        self.B, self.device = int(B), torch.device(device)
+        self._dtype = np.dtype(_lib.DetPolicy)
+        assert self._dtype.itemsize == ops.DET_POLICY_BYTES == 40
+        n = ops.DET_POLICY_BYTES * self.B
+        self.table = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        cuda = self.table.is_cuda
+        self._ring = [torch.zeros(n, dtype=torch.uint8) for _ in range(4 if cuda else 1)]
+        if cuda:
+            self._ring = [h.pin_memory() for h in self._ring]
+        self._done = [None] * len(self._ring)
+        self._at = 0
+        self._rows, self._dirty = [], False                          # what the device table holds (all zero: no rows)
+
+    def set_rows(self, records):
+        """Rows 0..n-1 of the next tick (host side only): one ops.det_policy_record each; rows n..B-1 report nothing.  Rows equal
+        to what the device table already holds (the steady state: the same streams in the same rows) cost nothing: upload()
+        then copies nothing."""
+        assert len(records) <= self.B
+        records = list(records)
+        if records == self._rows:
+            return
+        self._rows, self._dirty = records, True
+        self._at = (self._at + 1) % len(self._ring)
+        if self._done[self._at] is not None:
+            self._done[self._at].synchronize()                       # (only when the device is a whole ring of ticks behind)
+        host = self._ring[self._at]
+        host.zero_()
+        table = host.numpy().view(self._dtype)
+        for b, r in enumerate(records):
+            table[b] = r
+
+    def upload(self):
+        """The rows of the last set_rows -> the device table: ONE non-blocking copy on the current stream (none if they are there)."""
+        if not self._dirty:
+            return
+        self._dirty = False
+        self.table.copy_(self._ring[self._at], non_blocking=True)
+        if self.table.is_cuda:
+            ev = self._done[self._at] or torch.cuda.Event()
+            ev.record()
+            self._done[self._at] = ev
+
+
 def _nhwc_of(t, like):
     """NHWC storage of a caller-supplied NCHW-shaped feature tensor, in the plan's dtype."""
     u = t.permute(0, 2, 3, 1)

@@ -716,6 +716,48 @@ def postprocess(pred, num_classes, conf_thre, nms_thre, ws=None):
     return ws.det, ws.index, ws.count
 
 
+DET_POLICY_BYTES = C.sizeof(_lib.DetPolicy)
+
+
+def det_policy_record(conf_thre, nms_thre, classes=None, class_agnostic=False, max_candidates=0, max_det=0):
+    """One sy_det_policy as the tuple a numpy view of dtype(_lib.DetPolicy) takes.  classes: iterable of class ids (< 128) or
+    None = every bit set.  No validation here (DetectionPolicy does it)."""
+    if classes is None:
+        mask = (0xffffffff,) * 4
+    else:
+        bits = 0
+        for c in classes:
+            bits |= 1 << int(c)
+        mask = tuple((bits >> (32 * w)) & 0xffffffff for w in range(4))
+    return (float(conf_thre), float(nms_thre), _lib.DET_AGNOSTIC if class_agnostic else 0, int(max_candidates), int(max_det), 0, mask)
+
+
+def det_policy_table(records, device):
+    """B records (det_policy_record) -> the device table sy_postprocess_rows reads: uint8 [B * 40].  A blocking copy; the
+    per-tick tables of the detectors are engine.PolicyTable."""
+    import numpy as np
+    host = np.zeros(len(records), dtype=np.dtype(_lib.DetPolicy))
+    for b, r in enumerate(records):
+        host[b] = r
+    return torch.from_numpy(host.view(np.uint8)).to(device)
+
+
+def postprocess_rows(pred, num_classes, table, ws=None):
+    """sy_postprocess_rows: postprocess() with one sy_det_policy per batch row.  table: uint8 device tensor of B * 40 bytes (or
+    an object with such a `.table`, engine.PolicyTable).  Returns (det, index, count) of `ws` as postprocess() does."""
+    assert pred.dtype == torch.float32 and pred.is_contiguous() and pred.shape[2] == 5 + num_classes
+    B, A = pred.shape[:2]
+    table = getattr(table, "table", table)
+    assert table.dtype == torch.uint8 and table.is_contiguous() and table.numel() == B * DET_POLICY_BYTES
+    assert table.device == pred.device
+    if ws is None or ws.B != B or ws.A != A:
+        ws = PostprocessWorkspace(B, A, pred.device)
+    check(_lib.lib().sy_postprocess_rows(pred.data_ptr(), B, A, num_classes, table.data_ptr(), ws.max_det, ws.det.data_ptr(),
+                                         ws.index.data_ptr(), ws.count.data_ptr(), ws.ws.data_ptr(), stream_of(pred)),
+          "sy_postprocess_rows")
+    return ws.det, ws.index, ws.count
+
+
 class TalLossWorkspace:
     """Device buffers of sy_tal_loss for a given (B, A): workspace, d_raw, losses[8], fg mask, level tables."""
 

@@ -22,7 +22,7 @@ import torch
 from . import ops
 from ._lib import PIX_NV12, pixel_format_code
 from .data import FramePairsU8, FrameRowsU8, FrameSurfacesU8, Surface, row_geometry
-from .postprocess import postprocess_device
+from .postprocess import DetectionPolicy, _as_policy, postprocess_device
 
 
 def inference(outputs, num_classes=8, conf_thre=0.01, nms_thresh=0.65, in_scale=0.5):
@@ -95,12 +95,17 @@ class StreamingDetector:
 
     Every frame is copied into the detector's own slot: its tape carries the frame pointer by value, so a per-frame pointer cannot
     ride in it.  A single camera whose decoder surfaces should be read in place (data.Surface) uses
-    MultiStreamDetector(batch=1, surfaces=True), whose pointers are table data."""
+    MultiStreamDetector(batch=1, surfaces=True), whose pointers are table data.
+
+    policy=DetectionPolicy(...): what counts as a detection beyond the two thresholds — a class list, class-agnostic NMS, caps on
+    the candidates and on the detections; the post step is then sy_postprocess_rows over a one-row table."""
 
     def __init__(self, model, frame_hw, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65, dtype="fp16",
-                 device="cuda", pixel_format="bgr"):
+                 device="cuda", pixel_format="bgr", policy=None):
         self.pixel_format = pixel_format
         self._frame_shape = frame_shape(frame_hw, pixel_format)      # (ValueError before anything is built)
+        self.policy = None if policy is None else _as_policy(policy)
+        row = None if policy is None else self.policy.record(num_classes, conf_thre, nms_thresh)
         self.model = model.to(device).eval().set_compute_dtype(dtype)
         self.device = torch.device(device)
         self.in_scale = in_scale
@@ -125,6 +130,11 @@ class StreamingDetector:
         self.plan = model._plans.inference(model.backbone, model.head, "on_pipe", self._in, owner=model, split_k=split_k)
         self._first = True
         self._post = lambda out: postprocess_device(out, num_classes, conf_thre, nms_thresh)   # one object: part of the tape key
+        if row is not None:
+            # a DetectionPolicy (class list, class-agnostic NMS, caps): the post step is sy_postprocess_rows over a one-row table
+            self._table = ops.det_policy_table([row], self.device)
+            self._ws = ops.PostprocessWorkspace(1, self.plan.A, self.device)
+            self._post = lambda out: ops.postprocess_rows(out, num_classes, self._table, self._ws)
 
     def warm_up(self, n=10):
         """streamyolo_det.py:113-120 (ten calls on a dummy frame; here they also build / tune the plan)."""
@@ -148,8 +158,11 @@ class StreamingDetector:
         with torch.no_grad():
             if self._first:                                   # node 'star': extra fan-in copies, through the wrappers
                 self._first = False
-                return inference(self.plan.run_stream(self._in, first=True), self.num_classes, self.conf_thre,
-                                 self.nms_thresh, self.in_scale)
+                out = self.plan.run_stream(self._in, first=True)
+                if self.policy is not None:
+                    det, _, cnt = self._post(out)
+                    return _parse(det, cnt, self.in_scale)
+                return inference(out, self.num_classes, self.conf_thre, self.nms_thresh, self.in_scale)
             # steady state: the ~140 launches of the frame (pack, network, decode, NMS) replayed from a launch tape
             det, _, cnt = self.plan.run_stream_taped(self._in, post=self._post, check_params=False)
             return _parse(det, cnt, self.in_scale)
@@ -208,11 +221,25 @@ class MultiStreamDetector:
         cam = det.open()
         (boxes, scores, labels, _, ids), = det([frame], [cam], frame_idx=[12], horizon=1.0)
 
+    policy=DetectionPolicy(...) (or True for the defaults) makes what counts as a detection per-stream data as well: the tape
+    holds sy_postprocess_rows, which reads one record per batch row — thresholds, the classes reported, class-agnostic NMS, caps
+    on the candidates and on the detections (engine.PolicyTable, uploaded beside the slot table).  open(policy=...) gives a
+    stream its own, set_policy(sid, policy) changes it between two ticks on the same tape; a stream without one follows the
+    detector's.  Without policy= the tape holds sy_postprocess as before and per-stream policies are a ValueError.
+
+        det = MultiStreamDetector(model, (1200, 1920), batch=8, policy=True); det.warm_up()
+        cars = det.open(policy=DetectionPolicy(conf_thre=0.3, classes=[2, 3]))
+        feed = det.open(policy=DetectionPolicy(class_agnostic=True, max_det=100))
+        det.set_policy(cars, DetectionPolicy(conf_thre=0.5, classes=[2]))
+
     Which frames go into a tick is the caller's scheduling policy."""
 
     def __init__(self, model, frame_hw, max_streams=16, batch=8, in_scale=0.5, num_classes=8, conf_thre=0.01, nms_thresh=0.65,
-                 dtype="fp16", device="cuda", max_frame_hw=None, pixel_format="bgr", surfaces=False, track=None):
+                 dtype="fp16", device="cuda", max_frame_hw=None, pixel_format="bgr", surfaces=False, track=None, policy=None):
         self.pixel_format, self.surfaces = pixel_format, bool(surfaces)
+        self.policy = None if policy is None or policy is False else _as_policy(policy)      # the default of its streams
+        if self.policy is not None:
+            self.policy.record(num_classes, conf_thre, nms_thresh)                  # (ValueError before anything is built)
         self._frame_shape = _stream_shape(frame_hw, pixel_format, self.surfaces)     # (ValueError before anything is built)
         if int(batch) < 1 or int(max_streams) < 1:
             raise ValueError("MultiStreamDetector: batch and max_streams must be positive")
@@ -254,6 +281,14 @@ class MultiStreamDetector:
         self.state = StreamSlots(self.plan, self.max_streams)
         self._ws = ops.PostprocessWorkspace(self.batch, self.plan.A, self.device)          # its own: results live until the next tick
         self._post = lambda out: ops.postprocess(out, num_classes, conf_thre, nms_thresh, self._ws)   # one object: part of the tape key
+        self.policies = None
+        self._pol = {}                                           # open stream id -> its sy_det_policy record
+        nms = self._post                                         # the NMS step of the tape: (det, index, cnt)
+        if self.policy is not None:
+            # per-stream policies: the tape holds sy_postprocess_rows, and what each row asks for is table data like its slot
+            from .engine import PolicyTable
+            self.policies = PolicyTable(self.batch, self.device)
+            nms = self._post = lambda out: ops.postprocess_rows(out, num_classes, self.policies, self._ws)
         self.track = TrackConfig() if track is True else (track or None)
         self.tracks = None
         if self.track is not None:
@@ -263,7 +298,7 @@ class MultiStreamDetector:
             self._track_prm = ops.track_params(cfg.match_iou_th, cfg.r, cfg.q, cfg.p_init, cfg.min_size)
 
             def post(out):                                       # the NMS, then the tracker on its output: one more launch
-                det, index, cnt = ops.postprocess(out, num_classes, conf_thre, nms_thresh, self._ws)
+                det, index, cnt = nms(out)
                 ops.track_update(det, cnt, self.state.row_slot, self.state.row_first, self.tracks.ticks, self.tracks.state,
                                  self._track_prm, self.tracks.out, self.tracks.out_id, self.tracks.out_cnt)
                 return det, index, cnt
@@ -275,10 +310,32 @@ class MultiStreamDetector:
         self._next_id = 0                                        # ids are never reused: a closed id stays invalid
 
     # ---- stream bookkeeping (host side only) --------------------------------------------------------------------
-    def open(self, frame_hw=None, pixel_format=None):
+    def _policy_record(self, policy):
+        """The table record of a stream's policy (None: the detector's default).  ValueError: the detector has no policy table,
+        or the policy does not fit it (class ids)."""
+        if self.policy is None:
+            if policy is None:
+                return None
+            raise ValueError("MultiStreamDetector: per-stream policies need a detector built with policy=... (True for the defaults)")
+        if policy is not None and not isinstance(policy, DetectionPolicy):
+            raise ValueError("MultiStreamDetector: policy must be a DetectionPolicy or None, got %r" % (policy,))
+        return (self.policy if policy is None else policy).record(self.num_classes, self.conf_thre, self.nms_thresh)
+
+    def set_policy(self, sid, policy):
+        """Stream `sid` reports by `policy` (a DetectionPolicy; None: the detector's default) from its next tick on.  Table data:
+        the launch tape stays the one it is.  ValueError — nothing changes — on a detector built without policy=."""
+        self._known(sid)
+        if self.policy is None:
+            raise ValueError("MultiStreamDetector: set_policy needs a detector built with policy=... (True for the defaults)")
+        self._pol[sid] = self._policy_record(policy)
+
+    def open(self, frame_hw=None, pixel_format=None, policy=None):
         """A new stream: its id.  Its first frame fuses with itself (`buffer = None`, streamyolo_det.py:150).  Mixed mode:
         frame_hw = (h, w) is this stream's camera size for its lifetime (None: the detector's frame_hw and in_scale) and
-        pixel_format its format (None: the detector's).  ValueError — nothing is taken — for what the detector cannot serve."""
+        pixel_format its format (None: the detector's).  policy: the stream's DetectionPolicy (None: the detector's; needs a
+        detector built with policy=; set_policy changes it later).  ValueError — nothing is taken — for what the detector
+        cannot serve."""
+        record = self._policy_record(policy)
         geom = (self.frame_hw, self.decimate, self.in_scale)
         if pixel_format is None:
             pixel_format = self.pixel_format
@@ -304,6 +361,8 @@ class MultiStreamDetector:
         self._geom[sid] = geom
         self._fmt[sid] = (pixel_format, shape)
         self._fidx[sid] = None
+        if record is not None:
+            self._pol[sid] = record
         return sid
 
     def _known(self, sid):
@@ -324,6 +383,7 @@ class MultiStreamDetector:
         del self._geom[sid]
         del self._fmt[sid]
         del self._fidx[sid]
+        self._pol.pop(sid, None)
 
     def warm_up(self, n=10):
         """streamyolo_det.py:113-120 on a dummy batch (no row carries a frame: no stream's state is written); builds, tunes and
@@ -339,6 +399,9 @@ class MultiStreamDetector:
         if self.tracks is not None:
             self.tracks.set_rows(())
             self.tracks.upload()
+        if self.policies is not None:
+            self.policies.set_rows(())
+            self.policies.upload()
         with torch.no_grad():
             for _ in range(max(int(n), 2)):                      # (a tuning + recording tick, then at least one replay)
                 self.plan.run_stream_slots_taped(self._in, self.state, post=self._post)
@@ -418,6 +481,9 @@ class MultiStreamDetector:
             self._in.upload()
         self.state.set_rows([self._slot_of[s] for s in sids], [self._first[s] for s in sids])
         self.state.upload()
+        if self.policies is not None:
+            self.policies.set_rows([self._pol[s] for s in sids])
+            self.policies.upload()
         if self.tracks is not None:
             rows = []
             for s, (idx, dt, horizon) in zip(sids, times):

@@ -50,6 +50,19 @@ per-round times and `add_ms_per_tick` (best minus best, to be read against the s
 one summarize() over everything the timed ticks added (sy_score_accumulate + the evaluation's host read).
 
     python tools/multistream_probe.py --score 1 --batches 1,8
+
+--policy 1: the tick of MultiStreamDetector(policy=True) — sy_postprocess_rows on the tape, one sy_det_policy per row — beside
+today's tick (sy_postprocess) at the same batch, two detectors over two copies of the model, in one process, alternating.  The
+rows detector is timed with default rows, with max_det=100 and with max_candidates=1024 at the detector's conf_thre = 0.01 (the
+realistic candidate count: ~1 % of the anchors), and the same three with conf_thre = 0 in the rows (EVERY anchor a candidate:
+the serial sweep at its full 185 chunks, where the caps shorten it); the policies are switched with set_policy between the timed
+runs, on the one tape.  Today's tick is timed twice per round (`today`, `today_again`): `today_spread_ms` over all of those
+rounds is what `rows_default_minus_today_ms` has to be read against.  Two controls over model copies of their own: `today_twin`, a
+second detector of today's kind, and `today_with_table`, a policy=True detector whose post step is swapped back to sy_postprocess
+before its tape is recorded (the table and its bookkeeping, but today's launches).  `nms_us`: the three NMS launches alone at the
+plan's anchor count on synthetic predictions (every anchor / 1 % of the anchors a candidate), both entry points and capped rows.
+
+    python tools/multistream_probe.py --policy 1 --batches 1,8
 """
 import argparse
 import json
@@ -86,6 +99,7 @@ def main():
     ap.add_argument("--track", type=int, default=0, help="1: the tracked tick beside the untracked tick of the same batch")
     ap.add_argument("--untracked-only", type=int, default=0, help="with --track 1: only the untracked tick (runs on older trees)")
     ap.add_argument("--score", type=int, default=0, help="1: the tick with and without DetectionScorer.add, and one summarize()")
+    ap.add_argument("--policy", type=int, default=0, help="1: the tick through sy_postprocess_rows (default and capped rows) beside today's")
     ap.add_argument("--tree", default=None, help="root of another checkout of the repository to import the package from")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -324,6 +338,126 @@ def main():
             res["rows"].append(row)
             emit()
             del det, scorer
+        print(emit())
+        return
+
+    if args.policy:
+        if args.mixed or args.surfaces or args.track or args.score or fmt != "bgr":
+            ap.error("--policy is a separate measurement")
+        from streamyolo_amd import DetectionPolicy, ops
+        from streamyolo_amd.streaming import MultiStreamDetector
+        res.update({"policy": True})
+        variants = {"rows_default": None, "rows_max_det100": DetectionPolicy(max_det=100),
+                    "rows_max_cand1024": DetectionPolicy(max_candidates=1024),
+                    "rows_conf0": DetectionPolicy(conf_thre=0.0), "rows_conf0_max_det100": DetectionPolicy(conf_thre=0.0, max_det=100),
+                    "rows_conf0_max_cand1024": DetectionPolicy(conf_thre=0.0, max_candidates=1024)}
+        for B in batches:
+            kw = dict(max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+            plain = MultiStreamDetector(model, hw, **kw)
+            plain.warm_up(args.warmup)
+            p_sids = [plain.open() for _ in range(B)]
+            twin = sy.build_model(args.model)                    # (its own plan: no tape is re-recorded when the ticks alternate)
+            twin.load_state_dict(model.state_dict(), strict=True)
+            rows = MultiStreamDetector(twin, hw, policy=True, **kw)
+            rows.warm_up(args.warmup)
+            r_sids = [rows.open() for _ in range(B)]
+            twin2 = sy.build_model(args.model)                   # the control: today's detector over a model copy of its own, as
+            twin2.load_state_dict(model.state_dict(), strict=True)   # the rows detector is (two plans are two tunings and placements)
+            plain2 = MultiStreamDetector(twin2, hw, **kw)
+            plain2.warm_up(args.warmup)
+            q_sids = [plain2.open() for _ in range(B)]
+
+            def today_twin():
+                plain2.detect_device(frames[:B], q_sids)
+            # second control: everything policy=True allocates and does per tick (table, pinned mirrors, set_rows), but today's
+            # three launches on the tape — the post step is swapped back before anything is recorded
+            twin3 = sy.build_model(args.model)
+            twin3.load_state_dict(model.state_dict(), strict=True)
+            mixed_det = MultiStreamDetector(twin3, hw, policy=True, **kw)
+            mixed_det._post = lambda out, d=mixed_det: ops.postprocess(out, d.num_classes, d.conf_thre, d.nms_thresh, d._ws)
+            mixed_det.warm_up(args.warmup)
+            m_sids = [mixed_det.open() for _ in range(B)]
+
+            def today_with_table():
+                mixed_det.detect_device(frames[:B], m_sids)
+
+            def today():
+                plain.detect_device(frames[:B], p_sids)
+
+            def rows_tick():
+                rows.detect_device(frames[:B], r_sids)
+            rounds = {k: [] for k in ["today", "today_again", "today_twin", "today_with_table"] + list(variants)}
+            stats = {}
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                today()
+                rounds["today"].append(timed(today, args.ticks)[0])
+                for k, pol in variants.items():
+                    for s in r_sids:
+                        rows.set_policy(s, pol)                  # table data: the tape stays
+                    rows_tick()
+                    rounds[k].append(timed(rows_tick, args.ticks)[0])
+                    if k not in stats:
+                        stats[k] = rows.detect_device(frames[:B], r_sids)[1][:B].cpu().tolist()
+                today_twin()
+                rounds["today_twin"].append(timed(today_twin, args.ticks)[0])
+                today_with_table()
+                rounds["today_with_table"].append(timed(today_with_table, args.ticks)[0])
+                today()
+                rounds["today_again"].append(timed(today, args.ticks)[0])   # the old path against itself: the spread of this box
+            row = {"batch": B, "active": B, "detections_per_row": stats,
+                   "detections_per_row_today": plain.detect_device(frames[:B], p_sids)[1][:B].cpu().tolist()}
+            for k, v in rounds.items():
+                row.update({k + "_ms_per_tick": min(v), k + "_ms_rounds": v})
+            both = rounds["today"] + rounds["today_again"]
+            row["today_spread_ms"] = max(both) - min(both)
+            row["today_vs_today_again_ms"] = abs(min(rounds["today"]) - min(rounds["today_again"]))
+            row["rows_default_minus_today_ms"] = min(rounds["rows_default"]) - min(both)
+            row["today_twin_minus_today_ms"] = min(rounds["today_twin"]) - min(both)
+            row["today_with_table_minus_today_ms"] = min(rounds["today_with_table"]) - min(both)
+            row["rows_default_minus_today_twin_ms"] = min(rounds["rows_default"]) - min(rounds["today_twin"])
+            # the NMS alone at this batch and the plan's anchor count on synthetic predictions (the network's own output leaves no
+            # detection on these frames): `dense` = every anchor a candidate, `one_percent` = 1 % of them over conf 0.01; --ticks
+            # calls (three launches each) replayed back to back from a launch tape between two events, launch gaps included
+            A, nc = rows.plan.A, 8
+            g = torch.Generator().manual_seed(5)
+            pred = torch.zeros(B, A, 5 + nc)
+            pred[..., 0] = torch.rand(B, A, generator=g) * hw[1] / 2
+            pred[..., 1] = torch.rand(B, A, generator=g) * hw[0] / 2
+            pred[..., 2:4] = torch.rand(B, A, 2, generator=g) * 200 + 8
+            pred[..., 4] = torch.rand(B, A, generator=g) * 0.5 + 0.25 + torch.arange(A)[None] * 2.0 ** -20
+            pred[..., 5:] = torch.rand(B, A, nc, generator=g)
+            sparse = pred.clone()
+            sparse[..., 4] = torch.where(torch.rand(B, A, generator=g) < 0.01, sparse[..., 4], torch.full((), 1e-4))
+            ws = ops.PostprocessWorkspace(B, A, dev)
+            rec = {"rows_default": DetectionPolicy(), "rows_max_det100": DetectionPolicy(max_det=100),
+                   "rows_max_cand1024": DetectionPolicy(max_candidates=1024),
+                   "rows_max_cand1024_max_det100": DetectionPolicy(max_candidates=1024, max_det=100),
+                   "rows_agnostic": DetectionPolicy(class_agnostic=True)}
+            row["nms_us"], row["nms_counts"] = {}, {}
+            for name, p in (("dense", pred.to(dev)), ("one_percent", sparse.to(dev))):
+                calls = {"today": lambda: ops.postprocess(p, nc, 0.01, 0.65, ws)}
+                for k, pol in rec.items():
+                    tab = ops.det_policy_table([pol.record(nc, 0.01, 0.65)] * B, dev)
+                    calls[k] = lambda tab=tab: ops.postprocess_rows(p, nc, tab, ws)
+                tapes = {}
+                for k, fn in calls.items():
+                    fn()
+                    row["nms_counts"][name + "/" + k] = ws.count.cpu().tolist()
+                    tapes[k] = _lib.NativeTape()
+                    with tapes[k]:
+                        for _ in range(args.ticks):
+                            fn()
+                stream = ops.stream_of(p)
+                us = {k: [] for k in calls}
+                for _ in range(args.rounds):                     # alternate
+                    for k, t in tapes.items():
+                        t.replay(stream, None)
+                        us[k].append(1e3 * timed(lambda: t.replay(stream, None), 3)[0] / args.ticks)
+                row["nms_us"][name] = {k: {"best": min(v), "rounds": v} for k, v in us.items()}
+                del tapes
+            res["rows"].append(row)
+            emit()
+            del plain, rows, twin, plain2, twin2, mixed_det, twin3
         print(emit())
         return
 
