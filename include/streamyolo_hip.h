@@ -662,6 +662,81 @@ SY_API int sy_score_match(const float* det, const int32_t* cnt, int B, int max_d
 SY_API int sy_score_accumulate(const void* state, int num_classes, int capacity, const sy_score_params* params, void* workspace,
                                double* precision, double* recall, double* overflow, void* stream);
 
+/* ---- drawing a tick's boxes, class labels and track ids into camera surfaces, in place --------------------------------
+ * The opposite direction of sy_frames_u8_pack_surfaces: ONE launch writes the outlines and label tabs of every batch row's
+ * box list into that row's BGR / RGB / NV12 / P010 surface in DEVICE memory, from the device tensors the tick produced — no
+ * host read.  Geometry and style are per-row table data (sy_overlay_row, DEVICE memory); the grid depends on (B, Hmax, Wmax)
+ * only, so one recorded launch serves any table contents.  Added to ABI 7 (nothing existing changed).
+ *
+ * Box lists.  layout 0: boxes = det [B, max_list, 7] (x1, y1, x2, y2, obj, class_conf, class; score = obj * class_conf in
+ *   fp32), sy_postprocess's output.  layout 1: boxes = [B, max_list, 6] (x1, y1, x2, y2, score, label) with ids [B, max_list],
+ *   sy_track_update's output.  cnt [B] is the live length; row b looks at its first
+ *       n = min(cnt[b], max_list, SY_OVERLAY_MAX_BOXES, row.max_boxes when > 0)       (cnt < 0 counts as 0)
+ *   entries.  SY_OVERLAY_MAX_BOXES = 256 is what a workgroup stages in LDS.
+ * Palette.  palette [num_classes][8] bytes: B, G, R, text value (0 or 255), Y, U, V, text luma (16 or 235).  The kernel does no
+ *   colour conversion: BGR / RGB surfaces take bytes 0..2 (RGB: in the order R, G, B) and a glyph pixel takes byte 3 in all
+ *   three channels; NV12 / P010 take byte 4 as luma and (5, 6) as (U, V), a glyph pixel takes byte 7 as luma and (128, 128).
+ * Labels.  class_text [num_classes][8]: glyph codes, 0xFF ends a name (NULL: no names).  glyphs [64][8]: an 8 x 8 bitmap font,
+ *   code c = ASCII 32 + c, one byte per glyph row, the MSB is the left pixel; a code in 64..254 is drawn blank.  A box whose
+ *   class is outside [0, num_classes) (NaN included) takes class 0's colours and has no name.
+ *
+ * The rendering rule (t = thickness clamped to 1..16, s = text_scale clamped to 0..4; all arithmetic on coordinates is fp32
+ * IEEE without contraction, then integer):
+ * 1. Rectangle.  With r(c) = floor(c / divisor + 0.5):  X1 = r(x1), Y1 = r(y1), X2 = r(x2) - 1, Y2 = r(y2) - 1, inclusive.
+ *    A box is skipped when any c or c / divisor + 0.5 is not finite, when X2 < X1 or Y2 < Y1, or when its score is below
+ *    min_score or NaN.  All of this is decided before clipping.  (r(c) is clamped to +-2^30 before it becomes an integer.)
+ * 2. Outline.  The pixels of [X1, X2] x [Y1, Y2] that are not in [X1 + t, X2 - t] x [Y1 + t, Y2 - t]: a box narrower than 2 t
+ *    is filled.
+ * 3. Label tab (s > 0).  The string is the class name, then — when there is a suffix — a space and the suffix.  flags bit 0
+ *    (SY_OVERLAY_ID; ignored when ids == NULL): the suffix is the decimal digits of id mod 100000 (the non-negative
+ *    remainder, no leading zeros).  Otherwise flags bit 1 (SY_OVERLAY_SCORE): min(max(int(100 * score), 0), 99) as two
+ *    digits, then '%' (100 * score in fp32, int() truncates).  Neither: the name alone.  A string of L glyphs (L <= 14; L == 0:
+ *    no tab) has a tab 8 s L pixels wide and 8 s high with its left edge at X1, on the rows Y1 - 8 s .. Y1 - 1 directly
+ *    above the box, or — when Y1 - 8 s < 0 — inside it on the rows Y1 .. Y1 + 8 s - 1.  The tab is filled with the class
+ *    colour; every set font bit is an s x s block of the text value.
+ * 4. Precedence.  Everything is opaque: a pixel takes the colour of the LOWEST list index k whose tab or outline covers it —
+ *    inside k's tab the glyph value or the fill, else the outline colour.  Lists come in descending score, so the best box
+ *    ends on top.  Nothing is blended, so nothing depends on the order of writes.
+ * 5. Clipping.  Drawing is clipped to [0, Ws) x [0, Hs).  (Hs <= Hmax and Ws <= Wmax is the caller's duty: the launch has no
+ *    workgroups for tiles beyond Hmax x Wmax, what lies there is not drawn.)
+ * 6. NV12 / P010.  Luma as above.  A chroma sample (one (U, V) pair per 2 x 2 luma block) is written iff at least one of its
+ *    four luma pixels is covered, and takes the (U, V) of the first covered one in raster order (x, y), (x + 1, y),
+ *    (x, y + 1), (x + 1, y + 1).  P010 stores every sample v as the little-endian word v << 8 (bytes 0, v): read back by
+ *    sy_frames_u8_pack_surfaces' high-byte rule it is the same 8-bit sample.
+ * 7. Untouched bytes.  No byte the rule leaves uncovered is written at all: uncovered pixels, the bytes between a row's
+ *    payload and its pitch, padded luma rows, anything between the planes.  Drawing in place costs only what is drawn.
+ *
+ * Kernel shape: a gather.  A workgroup of 256 threads owns one SY_OVERLAY_TILE_H x SY_OVERLAY_TILE_W tile of one row's surface
+ * (a wavefront's stores are runs of one surface row; in the two-plane formats a thread owns one 2 x 2 block with its chroma
+ * sample), resolves the row's first n boxes (one per thread), compacts — order kept — those whose rectangle or tab meets the
+ * tile into LDS and leaves without touching memory when none does.  No atomics; no thread writes a pixel it does not own.
+ *
+ * Status: SY_ERR_ARG for rows / boxes / cnt / palette / glyphs == NULL, B / max_list / num_classes / Hmax / Wmax <= 0, a
+ * layout other than 0 or 1; SY_ERR_UNSUPPORTED for num_classes > 128 or B > 65535.  The host cannot see the table: a
+ * descriptor no surface can have (plane0 == NULL, Hs or Ws <= 0, an unknown format, odd NV12 / P010 sizes, a pitch — either
+ * one — below the row's bytes, a negative chroma_stride) is skipped on the device, never written through. */
+#define SY_OVERLAY_MAX_BOXES 256    /* list entries a launch looks at per row: the LDS staging cap                        */
+#define SY_OVERLAY_TILE_W 64        /* pixels: the tile of one workgroup                                                   */
+#define SY_OVERLAY_TILE_H 16
+#define SY_OVERLAY_ID 1             /* sy_overlay_row::flags                                                               */
+#define SY_OVERLAY_SCORE 2
+typedef struct sy_overlay_row {     /* 64 bytes, one per batch row, DEVICE memory                                          */
+    uint8_t* plane0;                /* BGR / RGB pixels or the luma plane; NULL or Hs == 0: nothing is drawn for this row  */
+    uint8_t* plane1;                /* NV12 / P010 chroma plane; NULL: plane0 + row_stride * Hs.  Ignored for BGR / RGB    */
+    int32_t Hs, Ws, row_stride, chroma_stride;   /* as sy_frame_surf (chroma_stride 0 = row_stride)                        */
+    int32_t format;                 /* SY_PIX_BGR / RGB / NV12 / P010                                                      */
+    float divisor;                  /* box coordinate / divisor = surface pixel (detections: the row's in_scale; tracks: 1) */
+    float min_score;                /* boxes with score < min_score are not drawn                                          */
+    int32_t max_boxes;              /* > 0: at most the first max_boxes list entries are looked at; 0: the launch's cap    */
+    int32_t thickness;              /* outline width in pixels, 1..16 (clamped)                                            */
+    int32_t text_scale;             /* 0: no label tab; 1..4: glyph cells of 8*scale x 8*scale pixels (clamped)            */
+    int32_t flags;                  /* SY_OVERLAY_ID: the label ends with the track id; SY_OVERLAY_SCORE: with the score   */
+    int32_t reserved;               /* 0 */
+} sy_overlay_row;
+SY_API int sy_overlay_draw(const sy_overlay_row* rows, int B, int Hmax, int Wmax, const float* boxes, int layout, int max_list,
+                           const int32_t* ids, const int32_t* cnt, const uint8_t* palette, const uint8_t* class_text,
+                           int num_classes, const uint8_t* glyphs, void* stream);
+
 /* backward of sy_resize_nearest (scatter-add into the source grid) */
 SY_API int sy_resize_nearest_bwd(const void* dout, int N, int Ho, int Wo, int C, int lddo, int64_t dobs,
                           void* din, int Hi, int Wi, int lddi, int64_t dibs, int accumulate,

@@ -15,9 +15,11 @@ from .postprocess import DetectionPolicy, postprocess
 from .data import Surface
 from .streaming import MultiStreamDetector, StreamingDetector, TrackConfig
 from .scoring import DetectionScorer, score_coco
+from .overlay import OverlayStyle, draw_detections
 
 __all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model", "DeviceGradScaler",
-           "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig", "DetectionPolicy", "DetectionScorer", "score_coco"]
+           "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig", "DetectionPolicy", "DetectionScorer", "score_coco",
+           "OverlayStyle", "draw_detections"]
 __version__ = "0.1.0"
 
 MODEL_ZOO = {

@@ -144,6 +144,19 @@ SCORE_LAYOUT = {"nms": 0, "track": 1, "xywh": 2}          # SY_SCORE_LAYOUT_*
 SCORE_RECORD = [("score_bits", "<u4"), ("seq", "<u4"), ("matched", "<u8"), ("ignored", "<u8"), ("rank", "<i4"), ("reserved", "<i4")]
 
 
+class OverlayRow(C.Structure):
+    """sy_overlay_row (include/streamyolo_hip.h): 64 bytes of DEVICE memory per batch row."""
+    _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("row_stride", C.c_int32),
+                ("chroma_stride", C.c_int32), ("format", C.c_int32), ("divisor", C.c_float), ("min_score", C.c_float),
+                ("max_boxes", C.c_int32), ("thickness", C.c_int32), ("text_scale", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+OVERLAY_MAX_BOXES = 256                        # SY_OVERLAY_MAX_BOXES
+OVERLAY_TILE = (16, 64)                        # (SY_OVERLAY_TILE_H, SY_OVERLAY_TILE_W): the pixels one workgroup owns
+OVERLAY_ID, OVERLAY_SCORE = 1, 2               # sy_overlay_row.flags
+
+
 class ScoreParams(C.Structure):
     """sy_score_params (include/streamyolo_hip.h)."""
     _fields_ = [("n_thr", C.c_int32), ("n_rec", C.c_int32), ("n_area", C.c_int32), ("n_maxdet", C.c_int32),
@@ -222,6 +235,7 @@ SIGNATURES = {
     "sy_score_reset": (_I, [_P, _I, _I, _P]),
     "sy_score_match": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _L, C.POINTER(ScoreParams), _P, _I, _I, _P]),
     "sy_score_accumulate": (_I, [_P, _I, _I, C.POINTER(ScoreParams), _P, _P, _P, _P, _P]),
+    "sy_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "sy_splitk_epilogue": (_I, [_P, _I, _L, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "sy_rows_add_f32": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
     "sy_pred_grad_fold_workspace_floats": (_L, [_I]),

@@ -352,6 +352,19 @@ class Surface:
     def device(self):
         return self.planes[0].device
 
+    def clone(self):
+        """A copy in memory of its own (on the same device, copied on the current stream) with the same format, sizes and
+        pitches: every plane gets its own allocation of rows x pitch bytes.  What to draw on (overlay.py) while the decoder may
+        still hold the original as a reference frame."""
+        planes = []
+        for p, pitch in zip(self.planes, (self.pitch, self.chroma_pitch)):
+            buf = torch.empty((p.shape[0], pitch), dtype=torch.uint8, device=p.device)
+            q = buf[:, :p.shape[1] * (3 if p.dim() == 3 else 1)]
+            q = q.unflatten(1, (p.shape[1], 3)) if p.dim() == 3 else q
+            q.copy_(p)
+            planes.append(q)
+        return Surface(planes[0] if len(planes) == 1 else tuple(planes), self.pixel_format)
+
 
 # sy_frame_surf (include/streamyolo_hip.h), one per batch row
 _SURF_DTYPE = np.dtype([("plane0", "<u8"), ("plane1", "<u8"), ("Hs", "<i4"), ("Ws", "<i4"), ("row_stride", "<i4"),

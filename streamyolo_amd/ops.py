@@ -530,6 +530,33 @@ def score_accumulate(state, num_classes, capacity, params, workspace, precision,
     return precision, recall
 
 
+OVERLAY_TILE = _lib.OVERLAY_TILE                 # (rows, columns) of pixels one workgroup of sy_overlay_draw owns
+
+
+def overlay_draw(table, B, max_hw, boxes, layout, ids, cnt, palette, class_text, glyphs):
+    """Draw every batch row's box list into its surface, in place (sy_overlay_draw): `table` = uint8 device tensor holding B
+    sy_overlay_row descriptors (64 bytes each: plane addresses, pitches, format, divisor and style; overlay.py fills and
+    validates them), max_hw = (Hmax, Wmax) no row's surface exceeds.  layout 0: boxes fp32 [>= B, L, 7] (sy_postprocess's det),
+    layout 1: fp32 [>= B, L, 6] with ids int32 [>= B, L] (sy_track_update's out / out_id); ids may be None.  cnt int32 [>= B].
+    palette uint8 [K, 8], class_text uint8 [K, 8], glyphs uint8 [64, 8].  One launch whose shape does not depend on the table."""
+    dev = table.device
+    assert table.dtype == torch.uint8 and table.is_contiguous() and table.numel() >= 64 * B and table.data_ptr() % 8 == 0
+    assert layout in (0, 1)
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 3 and boxes.shape[2] == (6 if layout else 7)
+    assert boxes.shape[0] >= B and boxes.device == dev
+    L = boxes.shape[1]
+    if ids is not None:
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape[:2]) == tuple(boxes.shape[:2]) and ids.device == dev
+    assert cnt.dtype == torch.int32 and cnt.is_contiguous() and cnt.numel() >= B and cnt.device == dev
+    assert palette.dtype == torch.uint8 and palette.is_contiguous() and palette.dim() == 2 and palette.shape[1] == 8 and palette.device == dev
+    K = palette.shape[0]
+    assert class_text.dtype == torch.uint8 and class_text.is_contiguous() and tuple(class_text.shape) == (K, 8) and class_text.device == dev
+    assert glyphs.dtype == torch.uint8 and glyphs.is_contiguous() and tuple(glyphs.shape) == (64, 8) and glyphs.device == dev
+    check(_lib.lib().sy_overlay_draw(table.data_ptr(), int(B), int(max_hw[0]), int(max_hw[1]), boxes.data_ptr(), int(layout), L,
+                                     _p(ids), cnt.data_ptr(), palette.data_ptr(), class_text.data_ptr(), K, glyphs.data_ptr(),
+                                     stream_of(table)), "sy_overlay_draw")
+
+
 def rows_add_f32(dst, src, rows, cols, ldd, lds, zero_src=False):
     """dst[r][:cols] += src[r][:cols] (fp32, row pitches ldd / lds in elements); zero_src: clear the source behind the read."""
     assert dst.dtype == torch.float32 and src.dtype == torch.float32

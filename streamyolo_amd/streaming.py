@@ -129,6 +129,8 @@ class StreamingDetector:
         split_k = str(dtype) not in ("fp32", "torch.float32") and os.environ.get("STREAMYOLO_STREAM_SPLITK", "1") != "0"
         self.plan = model._plans.inference(model.backbone, model.head, "on_pipe", self._in, owner=model, split_k=split_k)
         self._first = True
+        self._last = None                                            # (det, cnt) of the latest frame (draw)
+        self._overlay = self._style = None
         self._post = lambda out: postprocess_device(out, num_classes, conf_thre, nms_thresh)   # one object: part of the tape key
         if row is not None:
             # a DetectionPolicy (class list, class-agnostic NMS, caps): the post step is sy_postprocess_rows over a one-row table
@@ -159,13 +161,32 @@ class StreamingDetector:
             if self._first:                                   # node 'star': extra fan-in copies, through the wrappers
                 self._first = False
                 out = self.plan.run_stream(self._in, first=True)
-                if self.policy is not None:
-                    det, _, cnt = self._post(out)
-                    return _parse(det, cnt, self.in_scale)
-                return inference(out, self.num_classes, self.conf_thre, self.nms_thresh, self.in_scale)
+                det, _, cnt = self._post(out)                     # (without a policy: exactly inference(out, ...)'s NMS call)
+                self._last = (det, cnt)
+                return _parse(det, cnt, self.in_scale)
             # steady state: the ~140 launches of the frame (pack, network, decode, NMS) replayed from a launch tape
             det, _, cnt = self.plan.run_stream_taped(self._in, post=self._post, check_params=False)
+            self._last = (det, cnt)
             return _parse(det, cnt, self.in_scale)
+
+    def draw(self, surface, style=None):
+        """Draw the latest frame's detections into `surface` (a data.Surface, or a uint8 device tensor [H, W, 3] taken as BGR, of
+        the camera's size), in place, and return it: MultiStreamDetector.draw over this detector's one row."""
+        from .overlay import OverlayRows, OverlayStyle, as_target, draw_rows
+        if style is None:
+            style = self._style = self._style or OverlayStyle()
+        elif not isinstance(style, OverlayStyle):
+            raise ValueError("StreamingDetector: style must be an OverlayStyle, got %r" % (style,))
+        if self._last is None:
+            raise ValueError("StreamingDetector: no frame has been detected yet")
+        det, cnt = self._last
+        target = as_target(surface, det.device, self.frame_hw, "StreamingDetector")
+        if self._overlay is None:
+            self._overlay = OverlayRows(1, det.device)
+        self._overlay.set_row(0, target, self.in_scale, style)
+        self._overlay.upload()
+        draw_rows(self._overlay, self.frame_hw, det, 0, None, cnt, style)
+        return surface
 
 
 class MultiStreamDetector:
@@ -308,6 +329,9 @@ class MultiStreamDetector:
         self._first = {}                                         # open stream id -> its next frame starts a sequence
         self._free = list(range(self.max_streams))
         self._next_id = 0                                        # ids are never reused: a closed id stays invalid
+        self._row_of = {}                                        # stream id -> its batch row in the latest tick (draw)
+        self._last = None                                        # (det, cnt) of the latest tick
+        self._overlay = self._style = None                       # draw(): the sy_overlay_row table, the default style
 
     # ---- stream bookkeeping (host side only) --------------------------------------------------------------------
     def _policy_record(self, policy):
@@ -384,6 +408,7 @@ class MultiStreamDetector:
         del self._fmt[sid]
         del self._fidx[sid]
         self._pol.pop(sid, None)
+        self._row_of.pop(sid, None)
 
     def warm_up(self, n=10):
         """streamyolo_det.py:113-120 on a dummy batch (no row carries a frame: no stream's state is written); builds, tunes and
@@ -408,6 +433,7 @@ class MultiStreamDetector:
         torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
         for sid in self._first:
             self._first[sid] = True
+        self._row_of = {}
 
     # ---- ticks -----------------------------------------------------------------------------------------------
     def _check(self, frames, sids):
@@ -496,6 +522,7 @@ class MultiStreamDetector:
             self._first[s] = False
         with torch.no_grad():
             det, _, cnt = self.plan.run_stream_slots_taped(self._in, self.state, post=self._post)
+        self._last, self._row_of = (det, cnt), {s: b for b, s in enumerate(sids)}
         return det, cnt, n
 
     def detect_device(self, frames, sids, frame_idx=None, horizon=None):
@@ -541,6 +568,48 @@ class MultiStreamDetector:
             entries = [(self._slot_of[s], h, self._geom[s][0][1], self._geom[s][0][0]) for s, h in zip(part, hs[t0:])]
             res += self._parse_tracks(*self.tracks.forecast(entries, self._track_prm), len(part))
         return res
+
+    def draw(self, surfaces, sids, style=None):
+        """Draw the latest tick's results of the streams `sids` into `surfaces`, in place, and return them (overlay.py; the
+        rendering rule: include/streamyolo_hip.h).  A target is a data.Surface (bgr / rgb / nv12 / p010) or a uint8 device tensor
+        [H, W, 3] taken as BGR, of the stream's camera size, on the detector's device; it need not be the frame the tick read —
+        a decoder surface still held as a reference frame must NOT be drawn on: pass `[s.clone() for s in ...]`.  With tracking
+        the tracker's forecast output is drawn (camera coordinates, track ids), without it the detections (divided by the
+        stream's box divisor).  style: an overlay.OverlayStyle (None: the defaults).  ONE launch on the current stream behind
+        the tick, its table one non-blocking copy from pinned memory: no host read, no synchronisation, and not on the tick's
+        tape.  ValueError — before anything is written — for a stream without a frame in the latest tick, a stream named twice,
+        a target on another device or of another size."""
+        from .overlay import OverlayRows, OverlayStyle, as_target, draw_rows
+        surfaces, sids = list(surfaces), list(sids)
+        if len(surfaces) != len(sids):
+            raise ValueError("MultiStreamDetector: %d targets for %d stream ids" % (len(surfaces), len(sids)))
+        if style is None:
+            style = self._style = self._style or OverlayStyle()
+        elif not isinstance(style, OverlayStyle):
+            raise ValueError("MultiStreamDetector: style must be an OverlayStyle, got %r" % (style,))
+        if len(set(sids)) != len(sids):
+            raise ValueError("MultiStreamDetector: a stream id appears twice in one draw: %r" % (sids,))
+        targets = []
+        for t, sid in zip(surfaces, sids):
+            self._known(sid)
+            if sid not in self._row_of:
+                raise ValueError("MultiStreamDetector: stream %r had no frame in the latest tick" % (sid,))
+            targets.append(as_target(t, self.device if self._last is None else self._last[0].device, self._geom[sid][0],
+                                     "MultiStreamDetector"))
+        if not sids:
+            return surfaces
+        if self._overlay is None:
+            self._overlay = OverlayRows(self.batch, self._last[0].device)
+        self._overlay.clear()
+        for t, sid in zip(targets, sids):
+            self._overlay.set_row(self._row_of[sid], t, 1.0 if self.tracks is not None else self._geom[sid][2], style)
+        self._overlay.upload()
+        max_hw = self.max_frame_hw or self.frame_hw
+        if self.tracks is not None:
+            draw_rows(self._overlay, max_hw, self.tracks.out, 1, self.tracks.out_id, self.tracks.out_cnt, style)
+        else:
+            draw_rows(self._overlay, max_hw, self._last[0], 0, None, self._last[1], style)
+        return surfaces
 
     def __call__(self, frames, sids, frame_idx=None, horizon=None):
         """n camera frames (uint8 [H, W, 3] arrays or tensors; surfaces=True: data.Surface too) and the ids of their streams -> n (bboxes, scores, labels, None)

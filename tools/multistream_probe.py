@@ -63,6 +63,16 @@ before its tape is recorded (the table and its bookkeeping, but today's launches
 plan's anchor count on synthetic predictions (every anchor / 1 % of the anchors a candidate), both entry points and capped rows.
 
     python tools/multistream_probe.py --policy 1 --batches 1,8
+
+--overlay 1: drawing the tick's boxes into the camera frames on the device (MultiStreamDetector.draw, sy_overlay_draw; not on the
+tape), three things in one process, alternating.  `tick_ms_per_tick` / `tick_draw_ms_per_tick`: the tick alone and with one draw()
+of every row into a BGR frame behind it (style: min_score 0.01, at most 128 boxes; `boxes_drawn_per_row`), per-round times and
+`draw_ms_per_tick` (best minus best, to be read against the spread).  `overlay_kernel_us`: the launch alone on B 1200x1920 BGR
+and NV12 surfaces with 30 and with 256 boxes per row (a grid of 150 x 100 px / 56 x 36 px boxes with labels), --ticks launches
+replayed back to back from a launch tape between two events (the launch gaps included).  `clone_us`: the yardstick — a plain device
+copy of the same B surfaces (Surface.clone()), which is what drawing on the host would at least have to move once more.
+
+    python tools/multistream_probe.py --overlay 1 --batches 1,8
 """
 import argparse
 import json
@@ -100,6 +110,7 @@ def main():
     ap.add_argument("--untracked-only", type=int, default=0, help="with --track 1: only the untracked tick (runs on older trees)")
     ap.add_argument("--score", type=int, default=0, help="1: the tick with and without DetectionScorer.add, and one summarize()")
     ap.add_argument("--policy", type=int, default=0, help="1: the tick through sy_postprocess_rows (default and capped rows) beside today's")
+    ap.add_argument("--overlay", type=int, default=0, help="1: the tick with and without draw(), the overlay launch alone, Surface.clone()")
     ap.add_argument("--tree", default=None, help="root of another checkout of the repository to import the package from")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -287,6 +298,76 @@ def main():
             res["rows"].append(row)
             emit()
             del ticks, plain
+        print(emit())
+        return
+
+    if args.overlay:
+        if args.mixed or args.surfaces or args.track or args.score or args.policy or fmt != "bgr":
+            ap.error("--overlay is a separate measurement")
+        from streamyolo_amd import ops
+        from streamyolo_amd.data import Surface
+        from streamyolo_amd.overlay import OverlayRows, OverlayStyle
+        from streamyolo_amd.streaming import MultiStreamDetector
+        res.update({"overlay": True})
+        style = OverlayStyle(min_score=0.01, max_boxes=128)
+        for B in batches:
+            det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+            det.warm_up(args.warmup)
+            sids = [det.open() for _ in range(B)]
+            canvases = [f.clone() for f in frames[:B]]           # drawn on again and again: the cost does not depend on what is there
+
+            def tick_draw():
+                det.detect_device(frames[:B], sids)
+                det.draw(canvases, sids, style)
+            ticks = {"tick": lambda: det.detect_device(frames[:B], sids), "tick_draw": tick_draw}
+            rounds = {k: [] for k in ticks}
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                for k, fn in ticks.items():
+                    fn()
+                    rounds[k].append(timed(fn, args.ticks)[0])
+            row = {"batch": B, "active": B}
+            for k, v in rounds.items():
+                row.update({k + "_ms_per_tick": min(v), k + "_ms_rounds": v, k + "_spread_ms": max(v) - min(v)})
+            row["draw_ms_per_tick"] = min(rounds["tick_draw"]) - min(rounds["tick"])
+            r = det.detect_device(frames[:B], sids)
+            score = (r[0][:B, :128, 4] * r[0][:B, :128, 5] >= 0.01) & (torch.arange(128, device=dev)[None] < r[1][:B, None])
+            row["boxes_drawn_per_row"] = score.sum(dim=1).cpu().tolist()
+            # the launch alone, and the copy it stands against
+            nv12 = [bgr_to_nv12(f) for f in frames[:B]]
+            surfs = {"bgr": [Surface(f.clone(), "bgr") for f in frames[:B]],
+                     "nv12": [Surface((f[:hw[0]], f[hw[0]:]), "nv12") for f in nv12]}
+            pal, text, glyphs = style.tables(dev)
+            us, clone = {}, {}
+            for name, ss in surfs.items():
+                table = OverlayRows(B, dev)
+                for b, sf in enumerate(ss):
+                    table.set_row(b, sf, 1.0, style)
+                table._rows["max_boxes"] = 0                     # (the launch's cap: 256)
+                table.upload()
+                for k, (gw, bw, bh) in ((30, (6, 150, 100)), (256, (32, 56, 36))):
+                    g = torch.arange(256, device=dev, dtype=torch.float32)
+                    x1, y1 = (g % gw) * (hw[1] // gw) + 8, (g // gw) * (hw[0] // -(-256 // gw) if k == 256 else hw[0] // 5) + 40
+                    box = torch.stack([x1, y1, x1 + bw, y1 + bh, 1.0 - g / 512, g % 8], dim=1)
+                    lists = box[None].repeat(B, 1, 1).contiguous()
+                    ids_k = torch.arange(256, dtype=torch.int32, device=dev)[None].repeat(B, 1).contiguous()
+                    cnt_k = torch.full((B,), k, dtype=torch.int32, device=dev)
+
+                    def kernel():
+                        ops.overlay_draw(table.table, B, hw, lists, 1, ids_k, cnt_k, pal, text, glyphs)
+                    kernel()
+                    tape = _lib.NativeTape()
+                    with tape:
+                        for _ in range(args.ticks):
+                            kernel()
+                    stream = ops.stream_of(lists)
+                    tape.replay(stream, None)
+                    us["%s_%d" % (name, k)] = 1e3 * min(timed(lambda: tape.replay(stream, None), 3)[0] for _ in range(args.rounds)) / args.ticks
+                [sf.clone() for sf in ss]
+                clone[name] = 1e3 * min(timed(lambda: [sf.clone() for sf in ss], args.ticks)[0] for _ in range(args.rounds))
+            row["overlay_kernel_us"], row["clone_us"] = us, clone
+            res["rows"].append(row)
+            emit()
+            del ticks, det, surfs
         print(emit())
         return
 
