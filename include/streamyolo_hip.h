@@ -737,6 +737,78 @@ SY_API int sy_overlay_draw(const sy_overlay_row* rows, int B, int Hmax, int Wmax
                            const int32_t* ids, const int32_t* cnt, const uint8_t* palette, const uint8_t* class_text,
                            int num_classes, const uint8_t* glyphs, void* stream);
 
+/* ---- cropping a tick's boxes out of camera surfaces: a dense batch of fixed-size crops for a second stage ----------------
+ * The gather that mirrors sy_overlay_draw: the box lists the tick left in DEVICE memory become out [capacity, 3, Ch, Cw], every
+ * kept box resampled to Ch x Cw from its batch row's BGR / RGB / NV12 / P010 surface at the camera's own resolution — no host
+ * read.  Geometry and filters are per-row table data (sy_crop_row, DEVICE memory); both launches' grids depend on (capacity, Ch,
+ * Cw) only, so one recorded call serves any table and list contents.  Added to ABI 7 (nothing existing changed).
+ *
+ * boxes / layout / max_list / ids / cnt: exactly as sy_overlay_draw (layout 0: det [B, max_list, 7], score = obj * class_conf in
+ * fp32; layout 1: [B, max_list, 6] with ids [B, max_list] or NULL).  Row b looks at its first
+ *     n = min(cnt[b], max_list, SY_CROP_MAX_BOXES)                                          (cnt < 0 counts as 0)
+ * entries.
+ *
+ * The rule (all arithmetic on coordinates is fp32 IEEE without contraction up to the integer rectangle, integer from there on):
+ * 1. Rectangle.  Rule 1 of sy_overlay_draw: with r(c) = floor(c / divisor + 0.5) (clamped to +-2^30),  X1 = r(x1), Y1 = r(y1),
+ *    X2 = r(x2) - 1, Y2 = r(y2) - 1, inclusive.  An entry is skipped when any c or c / divisor + 0.5 is not finite, when X2 < X1
+ *    or Y2 < Y1, when its score is below min_score or NaN, when its class is NaN, outside [0, 128) or (as an integer, truncated)
+ *    has no bit in class_mask (bit c & 31 of word c >> 5), or when this unpadded rectangle does not meet [0, Ws) x [0, Hs).
+ * 2. Padding.  With W = X2 - X1 + 1 and px = (W * pad_q8 + 128) >> 8:  X1 -= px, X2 += px; the same in y with H.  (pad_q8 is
+ *    clamped to 0..256.)
+ * 3. Aspect (flags & SY_CROP_KEEP_ASPECT; otherwise each axis is stretched on its own).  With the padded W and H: when
+ *    W * Ch < H * Cw,  W' = ceil(H * Cw / Ch), X1 -= (W' - W) >> 1, X2 = X1 + W' - 1 (an odd growth puts the extra pixel on the
+ *    right); when W * Ch > H * Cw the same in y with H' = ceil(W * Ch / Cw) (the extra pixel at the bottom).
+ *    With or without the flag, an entry whose W or H now exceeds SY_CROP_MAX_SIDE is skipped.
+ * 4. Sampling: half-pixel centres, bilinear, 8-bit weights, edge replicate inside the rectangle.  For output column j:
+ *    n = (2 j + 1) W - Cw, d = 2 Cw, x0 = floor(n / d), f = n - x0 d, wx = (256 f + Cw) / d (integer division); the two taps are
+ *    the columns X1 + clamp(x0, 0, W - 1) and X1 + clamp(x0 + 1, 0, W - 1).  Rows likewise with i, H, Ch: wy and two tap rows.
+ *    Per channel:  v = ((256 - wx)(256 - wy) v00 + wx (256 - wy) v01 + (256 - wx) wy v10 + wx wy v11 + 32768) >> 16.
+ * 5. Taps.  A tap outside [0, Ws) x [0, Hs) is (fill[0], fill[1], fill[2]) as (B, G, R).  Inside it is the pixel's (B, G, R): BGR
+ *    as stored, RGB swapped, NV12 by the per-pixel conversion of sy_frames_u8_pack_fmt (nearest chroma: pair x >> 1 of chroma
+ *    row y >> 1; BT.601 limited range in the fixed point stated there), P010 the same on the HIGH bytes.  Conversion is per tap,
+ *    before interpolation: the crop equals the BGR rule applied to the converted frame.  No byte between a row's payload and its
+ *    pitch, in padded luma rows or between the planes is ever read.
+ * 6. Output.  Planar [slot][3][Ch][Cw]; planes are B, G, R, or R, G, B with SY_CROP_RGB_OUT.  SY_CROP_DT_U8 stores v; the float
+ *    types store (float(v) - mean3[c]) * scale3[c] computed in fp32 — a subtraction, then a multiplication, c the OUTPUT plane;
+ *    NULL = 0 / 1 — fp16 / bf16 rounded to nearest even.
+ * 7. Slots.  Kept entries are numbered with rows ascending, list index ascending within a row (no atomics: the same inputs
+ *    give the same slots).  A row contributes at most max_crops kept entries (max_crops > 0; the cap counts KEPT entries, the
+ *    entries skipped before them do not use it up).  Slot s < capacity receives its crop, out_index[s] = (batch row, list
+ *    index, id or -1 when ids == NULL, class) and out_rect[s] = (X1, Y1, X2, Y2) of the sampled rectangle (after 2 and 3; it
+ *    may leave the surface).  out_count = (min(total, capacity), total).  Slots at or past out_count[0] are not written at all,
+ *    in none of the three outputs.
+ * 8. Descriptors and status.  A descriptor no surface can have (the list of sy_overlay_draw: plane0 == NULL, Hs or Ws <= 0, an
+ *    unknown format, odd NV12 / P010 sizes, a pitch — either one — below the row's bytes, a negative chroma_stride) keeps
+ *    nothing and nothing of it is read.  SY_ERR_ARG for rows / boxes / cnt / out / out_index / out_rect / out_count == NULL,
+ *    B / max_list / capacity <= 0, a layout other than 0 or 1, unknown flag bits, an unknown out_dtype; SY_ERR_UNSUPPORTED for
+ *    Cw % 8 != 0, Ch or Cw outside 8..512, B > 1024.
+ *
+ * Kernel shape: two launches.  Plan: ONE workgroup of 256 threads walks the rows in order, thread k resolves list entry k, a
+ * ballot per wave and the four wave counts through LDS number the kept entries; it writes out_index, out_rect and out_count —
+ * which are also the gather's plan, there is no workspace.  Gather: grid (capacity, tiles of 256 x 8 output pixels); a workgroup
+ * whose slot is at or past out_count[0] leaves at once; the per-column (tap, tap, wx) triples go through LDS; a thread owns 8
+ * consecutive output columns of one row and writes each plane with one 8- / 16- / 32-byte run. */
+#define SY_CROP_MAX_BOXES 256       /* list entries a launch looks at per row                                              */
+#define SY_CROP_MAX_SIDE 16384      /* a padded rectangle wider or taller than this is skipped                              */
+#define SY_CROP_KEEP_ASPECT 1       /* flags                                                                               */
+#define SY_CROP_RGB_OUT 2           /* output planes in R, G, B order (default B, G, R)                                    */
+#define SY_CROP_DT_U8 3             /* out_dtype besides SY_DT_BF16 / SY_DT_F16 / SY_DT_F32                                */
+typedef struct sy_crop_row {        /* 72 bytes, one per batch row, DEVICE memory                                          */
+    const uint8_t* plane0;          /* BGR / RGB pixels or the luma plane; NULL or Hs == 0: the row keeps nothing          */
+    const uint8_t* plane1;          /* NV12 / P010 chroma plane; NULL: plane0 + row_stride * Hs.  Ignored for BGR / RGB    */
+    int32_t Hs, Ws, row_stride, chroma_stride;   /* as sy_frame_surf (chroma_stride 0 = row_stride)                        */
+    int32_t format;                 /* SY_PIX_BGR / RGB / NV12 / P010                                                      */
+    float divisor;                  /* box coordinate / divisor = surface pixel (detections: the row's in_scale; tracks: 1) */
+    float min_score;                /* entries with score < min_score are skipped                                          */
+    int32_t max_crops;              /* > 0: at most this many KEPT entries of the row; <= 0: no row cap                    */
+    int32_t pad_q8;                 /* context padding per side in 1/256 of the box side, 0..256 (clamped)                 */
+    uint8_t fill[4];                /* B, G, R of a tap outside the surface; byte 3 = 0                                    */
+    uint32_t class_mask[4];         /* as sy_det_policy: bit c & 31 of word c >> 5 set = class c is kept                   */
+} sy_crop_row;
+SY_API int sy_crop_gather(const sy_crop_row* rows, int B, const float* boxes, int layout, int max_list, const int32_t* ids,
+                          const int32_t* cnt, int Ch, int Cw, int flags, int out_dtype, const float* mean3, const float* scale3,
+                          void* out, int capacity, int32_t* out_index, int32_t* out_rect, int32_t* out_count, void* stream);
+
 /* backward of sy_resize_nearest (scatter-add into the source grid) */
 SY_API int sy_resize_nearest_bwd(const void* dout, int N, int Ho, int Wo, int C, int lddo, int64_t dobs,
                           void* din, int Hi, int Wi, int lddi, int64_t dibs, int accumulate,

@@ -157,6 +157,18 @@ OVERLAY_TILE = (16, 64)                        # (SY_OVERLAY_TILE_H, SY_OVERLAY_
 OVERLAY_ID, OVERLAY_SCORE = 1, 2               # sy_overlay_row.flags
 
 
+class CropRow(C.Structure):
+    """sy_crop_row (include/streamyolo_hip.h): 72 bytes of DEVICE memory per batch row."""
+    _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("row_stride", C.c_int32),
+                ("chroma_stride", C.c_int32), ("format", C.c_int32), ("divisor", C.c_float), ("min_score", C.c_float),
+                ("max_crops", C.c_int32), ("pad_q8", C.c_int32), ("fill", C.c_uint8 * 4), ("class_mask", C.c_uint32 * 4)]
+
+
+CROP_MAX_BOXES, CROP_MAX_SIDE = 256, 16384     # SY_CROP_MAX_BOXES, SY_CROP_MAX_SIDE
+CROP_KEEP_ASPECT, CROP_RGB_OUT = 1, 2          # flags of sy_crop_gather
+CROP_DT_U8 = 3                                 # SY_CROP_DT_U8: out_dtype besides DT_BF16 / DT_F16 / DT_F32
+
+
 class ScoreParams(C.Structure):
     """sy_score_params (include/streamyolo_hip.h)."""
     _fields_ = [("n_thr", C.c_int32), ("n_rec", C.c_int32), ("n_area", C.c_int32), ("n_maxdet", C.c_int32),
@@ -236,6 +248,7 @@ SIGNATURES = {
     "sy_score_match": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _L, C.POINTER(ScoreParams), _P, _I, _I, _P]),
     "sy_score_accumulate": (_I, [_P, _I, _I, C.POINTER(ScoreParams), _P, _P, _P, _P, _P]),
     "sy_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "sy_crop_gather": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "sy_splitk_epilogue": (_I, [_P, _I, _L, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "sy_rows_add_f32": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
     "sy_pred_grad_fold_workspace_floats": (_L, [_I]),

@@ -51,8 +51,11 @@
 // (word >> 8: truncation, no rounding, no dithering) — the project's definition, no OpenCV conversion exists to pin it against.
 // The wide-load fast path is decided per row from BOTH planes' addresses and pitches; P010 takes the generic path only.
 #include "sy_pointwise.h"
+#include "sy_nv12.h"
 
 namespace {
+
+using namespace sy_nv12;                                         // Chroma, nv12_chroma, nv12_bgr, sat8
 
 // One frame after the load-time resize: what the per-pixel sampling needs besides the pixels.  Resolved from the camera size, the
 // decimate mode and the canvas by frame_geom() — on the host for sy_frames_u8_pack (one geometry per batch), on the device for
@@ -134,24 +137,7 @@ __device__ __forceinline__ float frame_at(const unsigned char* p, const FrameGeo
     return (float)(((int)r0[0] + (int)r0[3] + (int)r1[0] + (int)r1[3] + 2) >> 2);
 }
 
-// ---- NV12 (see the header): BT.601 limited range, int32 fixed point with 20 fractional bits.  No intermediate leaves int32:
-// |1220542 y'| <= 2.92e8, the chroma terms with the rounding constant are within [-1.62e8, 2.70e8].
-struct Chroma { int b, g, r; };         // the chroma terms of B, G, R with the rounding constant: once per (U, V) pair
-__device__ __forceinline__ Chroma nv12_chroma(int U, int V) {
-    const int u = U - 128, v = V - 128;
-    Chroma k;
-    k.b = 2116026 * u + (1 << 19);
-    k.g = -409993 * u - 852492 * v + (1 << 19);
-    k.r = 1673527 * v + (1 << 19);
-    return k;
-}
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-__device__ __forceinline__ void nv12_bgr(int Y, const Chroma& k, int o[3]) {
-    const int y = 1220542 * (Y - 16 < 0 ? 0 : Y - 16);
-    o[0] = sat8((y + k.b) >> 20);
-    o[1] = sat8((y + k.g) >> 20);
-    o[2] = sat8((y + k.r) >> 20);
-}
+// ---- NV12: Chroma, nv12_chroma, sat8 and nv12_bgr (the per-pixel conversion) live in sy_nv12.h, shared with crop.hip
 // Where the chroma plane of an NV12 image lies and how its samples are stored: the interleaved (U, V) plane at `uv` with `pitch`
 // bytes between rows; sample k of a row (either plane) is the byte at (k << sh) + sh.  sh = 0: NV12 proper.  sh = 1: P010 — 16-bit
 // little-endian words whose HIGH byte is the 8-bit sample (a step of 2 bytes and an offset of 1: the same arithmetic on other

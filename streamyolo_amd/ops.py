@@ -557,6 +557,41 @@ def overlay_draw(table, B, max_hw, boxes, layout, ids, cnt, palette, class_text,
                                      stream_of(table)), "sy_overlay_draw")
 
 
+CROP_DTYPE = {torch.uint8: _lib.CROP_DT_U8, torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
+
+
+def crop_gather(table, B, boxes, layout, ids, cnt, out, out_index, out_rect, out_count, flags=0, mean=None, scale=None):
+    """Crop every batch row's kept list entries out of its surface into `out` [capacity, 3, Ch, Cw] (uint8, fp32, fp16 or bf16),
+    resampled by the rule of include/streamyolo_hip.h (sy_crop_gather): `table` = uint8 device tensor holding B sy_crop_row
+    descriptors (72 bytes each: plane addresses, pitches, format, divisor, filters, padding, fill; crops.py fills and validates
+    them).  layout 0: boxes fp32 [>= B, L, 7] (sy_postprocess's det), layout 1: fp32 [>= B, L, 6] with ids int32 [>= B, L]
+    (sy_track_update's out / out_id); ids may be None.  cnt int32 [>= B].  out_index / out_rect int32 [capacity, 4], out_count
+    int32 [2].  flags: CROP_KEEP_ASPECT | CROP_RGB_OUT; mean / scale: None or fp32 [3] device tensors in output plane order.  Two
+    launches whose shapes do not depend on the table or the lists; slots at or past out_count[0] are not written."""
+    dev = table.device
+    assert table.dtype == torch.uint8 and table.is_contiguous() and table.numel() >= 72 * B and table.data_ptr() % 8 == 0
+    assert layout in (0, 1)
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 3 and boxes.shape[2] == (6 if layout else 7)
+    assert boxes.shape[0] >= B and boxes.device == dev
+    L = boxes.shape[1]
+    if ids is not None:
+        assert ids.dtype == torch.int32 and ids.is_contiguous() and tuple(ids.shape[:2]) == tuple(boxes.shape[:2]) and ids.device == dev
+    assert cnt.dtype == torch.int32 and cnt.is_contiguous() and cnt.numel() >= B and cnt.device == dev
+    assert out.dtype in CROP_DTYPE and out.is_contiguous() and out.dim() == 4 and out.shape[1] == 3 and out.device == dev
+    assert out.data_ptr() % 16 == 0
+    cap, _, Ch, Cw = out.shape
+    for t in (out_index, out_rect):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (cap, 4) and t.device == dev
+    assert out_count.dtype == torch.int32 and out_count.is_contiguous() and out_count.numel() == 2 and out_count.device == dev
+    for t in (mean, scale):
+        if t is not None:
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 3 and t.device == dev
+    check(_lib.lib().sy_crop_gather(table.data_ptr(), int(B), boxes.data_ptr(), int(layout), L, _p(ids), cnt.data_ptr(), Ch, Cw,
+                                    int(flags), CROP_DTYPE[out.dtype], _p(mean), _p(scale), out.data_ptr(), cap,
+                                    out_index.data_ptr(), out_rect.data_ptr(), out_count.data_ptr(), stream_of(table)),
+          "sy_crop_gather")
+
+
 def rows_add_f32(dst, src, rows, cols, ldd, lds, zero_src=False):
     """dst[r][:cols] += src[r][:cols] (fp32, row pitches ldd / lds in elements); zero_src: clear the source behind the read."""
     assert dst.dtype == torch.float32 and src.dtype == torch.float32

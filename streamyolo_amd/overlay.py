@@ -176,12 +176,14 @@ def as_target(target, device=None, hw=None, who="draw"):
 class OverlayRows:
     """The table of sy_overlay_row descriptors of `batch` rows: one device buffer with a ring of pinned host mirrors, upload() is a
     single non-blocking copy on the current stream (as data.FrameRowsU8).  A row nobody set draws nothing."""
+    _DTYPE = _OVERLAY_DTYPE                                          # the record (crops.CropRows: sy_crop_row)
 
     def __init__(self, batch, device):
         self.batch, dev = int(batch), torch.device(device)
-        self.table = torch.zeros(64 * self.batch, dtype=torch.uint8, device=dev)
-        self._rows = np.zeros(self.batch, dtype=_OVERLAY_DTYPE)
-        self._ring = [torch.zeros(64 * self.batch, dtype=torch.uint8) for _ in range(4 if dev.type == "cuda" else 1)]
+        nbytes = self._DTYPE.itemsize * self.batch
+        self.table = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self._rows = np.zeros(self.batch, dtype=self._DTYPE)
+        self._ring = [torch.zeros(nbytes, dtype=torch.uint8) for _ in range(4 if dev.type == "cuda" else 1)]
         if dev.type == "cuda":
             self._ring = [h.pin_memory() for h in self._ring]
         self._done = [None] * len(self._ring)

@@ -131,6 +131,7 @@ class StreamingDetector:
         self._first = True
         self._last = None                                            # (det, cnt) of the latest frame (draw)
         self._overlay = self._style = None
+        self._crop_rows, self._crop_spec, self._crop_out = None, None, None  # crops(): the sy_crop_row table, the default spec, crops.CropCache
         self._post = lambda out: postprocess_device(out, num_classes, conf_thre, nms_thresh)   # one object: part of the tape key
         if row is not None:
             # a DetectionPolicy (class list, class-agnostic NMS, caps): the post step is sy_postprocess_rows over a one-row table
@@ -187,6 +188,27 @@ class StreamingDetector:
         self._overlay.upload()
         draw_rows(self._overlay, self.frame_hw, det, 0, None, cnt, style)
         return surface
+
+    def crops(self, surface, spec=None):
+        """Crop the latest frame's detections out of `surface` (a data.Surface, or a uint8 device tensor [H, W, 3] taken as BGR,
+        of the camera's size) -> crops.Crops: MultiStreamDetector.crops over this detector's one row (row_sids = (0,))."""
+        from .crops import CropCache, CropRows, CropSpec, as_source, check_spec, gather_rows
+        if spec is None:
+            spec = self._crop_spec = self._crop_spec or CropSpec()
+        check_spec(spec, "StreamingDetector")
+        if self._last is None:
+            raise ValueError("StreamingDetector: no frame has been detected yet")
+        det, cnt = self._last
+        source = as_source(surface, det.device, self.frame_hw, "StreamingDetector")
+        if self._crop_rows is None:
+            self._crop_rows = CropRows(1, det.device)
+        if self._crop_out is None:
+            self._crop_out = CropCache()
+        out = self._crop_out.get(spec, 1, det.device)
+        out.row_sids, spec = (0,), out.spec
+        self._crop_rows.set_row(0, source, self.in_scale, spec)
+        self._crop_rows.upload()
+        return gather_rows(self._crop_rows, det, 0, None, cnt, spec, out)
 
 
 class MultiStreamDetector:
@@ -332,6 +354,7 @@ class MultiStreamDetector:
         self._row_of = {}                                        # stream id -> its batch row in the latest tick (draw)
         self._last = None                                        # (det, cnt) of the latest tick
         self._overlay = self._style = None                       # draw(): the sy_overlay_row table, the default style
+        self._crop_rows, self._crop_spec, self._crop_out = None, None, None  # crops(): the sy_crop_row table, the default spec, crops.CropCache
 
     # ---- stream bookkeeping (host side only) --------------------------------------------------------------------
     def _policy_record(self, policy):
@@ -610,6 +633,57 @@ class MultiStreamDetector:
         else:
             draw_rows(self._overlay, max_hw, self._last[0], 0, None, self._last[1], style)
         return surfaces
+
+    def crops(self, surfaces, sids, spec=None):
+        """Crop the latest tick's results of the streams `sids` out of `surfaces` -> crops.Crops (images [capacity, 3, Ch, Cw],
+        index, rect, count: device tensors; the rule: include/streamyolo_hip.h).  A source is what draw() takes as a target — a
+        data.Surface (bgr / rgb / nv12 / p010) or a uint8 device tensor [H, W, 3] taken as BGR, of the stream's camera size, on
+        the detector's device — and is only read: the decoder's own surface will do.  With tracking the tracker's forecast
+        output is cropped (camera coordinates, track ids in index[:, 2]), without it the detections (divided by the stream's box
+        divisor).  spec: a crops.CropSpec (None: the defaults).  Crops come with batch rows ascending and list index ascending
+        within a row; index[:, 0] is the BATCH ROW and the result's row_sids[b] names the stream that row served (None: not
+        asked for).  ONE C call on the current stream behind the tick (two launches), its table one non-blocking copy from
+        pinned memory: no host read, no synchronisation, and not on the tick's tape.  The result's tensors are allocated once
+        per spec VALUE (a CropSpec built again with the same arguments reuses them; the detector keeps those of its four most
+        recently used specs) and overwritten by the next crops() with an equal spec.  ValueError — before anything is written — for a stream
+        without a frame in the latest tick, a stream named twice, a source on another device or of another size."""
+        from .crops import CropCache, CropRows, CropSpec, as_source, check_spec, gather_rows
+        surfaces, sids = list(surfaces), list(sids)
+        if len(surfaces) != len(sids):
+            raise ValueError("MultiStreamDetector: %d sources for %d stream ids" % (len(surfaces), len(sids)))
+        if spec is None:
+            spec = self._crop_spec = self._crop_spec or CropSpec()
+        check_spec(spec, "MultiStreamDetector")
+        if len(set(sids)) != len(sids):
+            raise ValueError("MultiStreamDetector: a stream id appears twice in one crops: %r" % (sids,))
+        sources = []
+        for t, sid in zip(surfaces, sids):
+            self._known(sid)
+            if sid not in self._row_of:
+                raise ValueError("MultiStreamDetector: stream %r had no frame in the latest tick" % (sid,))
+            sources.append(as_source(t, self.device if self._last is None else self._last[0].device, self._geom[sid][0],
+                                     "MultiStreamDetector"))
+        dev = self.device if self._last is None else self._last[0].device
+        if self._crop_out is None:
+            self._crop_out = CropCache()
+        out = self._crop_out.get(spec, self.batch, dev)
+        spec = out.spec                                          # (equal by value; the one whose device tables exist)
+        row_sids = [None] * self.batch
+        if not sids:
+            out.count.zero_()
+            out.row_sids = tuple(row_sids)
+            return out
+        if self._crop_rows is None:
+            self._crop_rows = CropRows(self.batch, dev)
+        self._crop_rows.clear()
+        for t, sid in zip(sources, sids):
+            row_sids[self._row_of[sid]] = sid
+            self._crop_rows.set_row(self._row_of[sid], t, 1.0 if self.tracks is not None else self._geom[sid][2], spec)
+        self._crop_rows.upload()
+        out.row_sids = tuple(row_sids)
+        if self.tracks is not None:
+            return gather_rows(self._crop_rows, self.tracks.out, 1, self.tracks.out_id, self.tracks.out_cnt, spec, out)
+        return gather_rows(self._crop_rows, self._last[0], 0, None, self._last[1], spec, out)
 
     def __call__(self, frames, sids, frame_idx=None, horizon=None):
         """n camera frames (uint8 [H, W, 3] arrays or tensors; surfaces=True: data.Surface too) and the ids of their streams -> n (bboxes, scores, labels, None)

@@ -73,6 +73,18 @@ replayed back to back from a launch tape between two events (the launch gaps inc
 copy of the same B surfaces (Surface.clone()), which is what drawing on the host would at least have to move once more.
 
     python tools/multistream_probe.py --overlay 1 --batches 1,8
+
+--crops 1: cropping the tick's boxes out of the camera frames on the device (MultiStreamDetector.crops, sy_crop_gather; not on the
+tape), three things in one process, alternating.  `tick_ms_per_tick` / `tick_crops_ms_per_tick`: the tick alone and with one
+crops() of every row's BGR frame behind it (64 x 64 fp16 crops, min_score 0.01, at most 32 per row; `boxes_cropped_per_row`),
+per-round times and `crops_ms_per_tick` (best minus best, to be read against the spread).  `crop_kernel_us`: the call alone (its
+two launches) on B 1200x1920 BGR and NV12 surfaces for 32 and 256 crops in all (spread evenly over the B rows; synthetic lists
+of 40..112 x 30..110 px boxes on a grid) of 64 x 64 and of 224 x 224 fp16, keep-aspect with 10 % padding, --ticks calls replayed
+back to back from a launch tape between two events (the launch gaps included).  `copy_us`: the yardstick — a plain device copy
+of a tensor the size of the crops written, the bytes any method must store — timed the same way (sy_view_copy replayed from a
+launch tape); `copy_eager_us`: torch's copy_ of the same tensor issued eagerly.
+
+    python tools/multistream_probe.py --crops 1 --batches 1,8
 """
 import argparse
 import json
@@ -111,6 +123,7 @@ def main():
     ap.add_argument("--score", type=int, default=0, help="1: the tick with and without DetectionScorer.add, and one summarize()")
     ap.add_argument("--policy", type=int, default=0, help="1: the tick through sy_postprocess_rows (default and capped rows) beside today's")
     ap.add_argument("--overlay", type=int, default=0, help="1: the tick with and without draw(), the overlay launch alone, Surface.clone()")
+    ap.add_argument("--crops", type=int, default=0, help="1: the tick with and without crops(), the crop call alone, a copy of the crops' bytes")
     ap.add_argument("--tree", default=None, help="root of another checkout of the repository to import the package from")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -365,6 +378,96 @@ def main():
                 [sf.clone() for sf in ss]
                 clone[name] = 1e3 * min(timed(lambda: [sf.clone() for sf in ss], args.ticks)[0] for _ in range(args.rounds))
             row["overlay_kernel_us"], row["clone_us"] = us, clone
+            res["rows"].append(row)
+            emit()
+            del ticks, det, surfs
+        print(emit())
+        return
+
+    if args.crops:
+        if args.mixed or args.surfaces or args.track or args.score or args.policy or args.overlay or fmt != "bgr":
+            ap.error("--crops is a separate measurement")
+        from streamyolo_amd import ops
+        from streamyolo_amd.crops import CropRows, Crops, CropSpec
+        from streamyolo_amd.data import Surface
+        from streamyolo_amd.streaming import MultiStreamDetector
+        res.update({"crops": True})
+        tick_spec = CropSpec(size=(64, 64), pad=0.1, min_score=0.01, max_per_stream=32)
+        for B in batches:
+            det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+            det.warm_up(args.warmup)
+            sids = [det.open() for _ in range(B)]
+
+            def tick_crops():
+                det.detect_device(frames[:B], sids)
+                det.crops(frames[:B], sids, tick_spec)
+            ticks = {"tick": lambda: det.detect_device(frames[:B], sids), "tick_crops": tick_crops}
+            rounds = {k: [] for k in ticks}
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                for k, fn in ticks.items():
+                    fn()
+                    rounds[k].append(timed(fn, args.ticks)[0])
+            row = {"batch": B, "active": B}
+            for k, v in rounds.items():
+                row.update({k + "_ms_per_tick": min(v), k + "_ms_rounds": v, k + "_spread_ms": max(v) - min(v)})
+            row["crops_ms_per_tick"] = min(rounds["tick_crops"]) - min(rounds["tick"])
+            det.detect_device(frames[:B], sids)
+            got = det.crops(frames[:B], sids, tick_spec)
+            row["boxes_cropped_per_row"] = torch.bincount(got.index[:int(got.count[0]), 0], minlength=B).cpu().tolist()
+            # the call alone, and the copy it stands against
+            nv12 = [bgr_to_nv12(f) for f in frames[:B]]
+            surfs = {"bgr": [Surface(f, "bgr") for f in frames[:B]],
+                     "nv12": [Surface((f[:hw[0]], f[hw[0]:]), "nv12") for f in nv12]}
+            us, copy, copy_eager, rounds_us = {}, {}, {}, {}
+            for side in (64, 224):
+                for total in (32, 256):
+                    per = total // B                             # boxes per row: a grid over the frame, sizes cycling
+                    spec = CropSpec(size=(side, side), pad=0.1, capacity=total)
+                    g = torch.arange(per, device=dev, dtype=torch.float32)
+                    gw = max(int(per ** 0.5), 1)
+                    x1, y1 = (g % gw) * ((hw[1] - 160) // gw) + 8, (g // gw) * ((hw[0] - 160) // -(-per // gw)) + 8
+                    box = torch.stack([x1, y1, x1 + 40 + (g % 7) * 12, y1 + 30 + (g % 5) * 20, 1.0 - g / 512, g % 8], dim=1)
+                    lists = box[None].repeat(B, 1, 1).contiguous()
+                    ids_k = torch.arange(per, dtype=torch.int32, device=dev)[None].repeat(B, 1).contiguous()
+                    cnt_k = torch.full((B,), per, dtype=torch.int32, device=dev)
+                    out = Crops.empty(spec, total, dev)
+                    twin = torch.empty_like(out.images)
+                    key = "%dx%d_%d" % (side, side, total)
+                    for name, ss in surfs.items():
+                        table = CropRows(B, dev)
+                        for b, sf in enumerate(ss):
+                            table.set_row(b, sf, 1.0, spec)
+                        table.upload()
+
+                        def kernel():
+                            ops.crop_gather(table.table, B, lists, 1, ids_k, cnt_k, out.images, out.index, out.rect, out.count, flags=spec.flags)
+                        kernel()
+                        assert out.count.tolist() == [total, total]
+                        tape = _lib.NativeTape()
+                        with tape:
+                            for _ in range(args.ticks):
+                                kernel()
+                        stream = ops.stream_of(lists)
+                        tape.replay(stream, None)
+                        v = [1e3 * timed(lambda: tape.replay(stream, None), 3)[0] / args.ticks for _ in range(args.rounds)]
+                        us["%s_%s" % (name, key)], rounds_us["%s_%s" % (name, key)] = min(v), v
+                    # the yardstick, timed the same way: the library's own copy kernel (16 bytes per thread) replayed from a tape;
+                    # beside it torch's copy_ issued eagerly, whose small sizes show the enqueue, not the copy
+                    def copy_kernel():
+                        _lib.check(_lib.lib().sy_view_copy(out.images.data_ptr(), 64, twin.data_ptr(), 64, out.images.numel() // 64, 64,
+                                                           _lib.DT_F16, 0, ops.stream_of(twin)), "sy_view_copy")
+                    copy_kernel()
+                    assert torch.equal(twin, out.images)
+                    tape = _lib.NativeTape()
+                    with tape:
+                        for _ in range(args.ticks):
+                            copy_kernel()
+                    stream = ops.stream_of(twin)
+                    tape.replay(stream, None)
+                    copy[key] = 1e3 * min(timed(lambda: tape.replay(stream, None), 3)[0] for _ in range(args.rounds)) / args.ticks
+                    copy_eager[key] = 1e3 * min(timed(lambda: twin.copy_(out.images), args.ticks)[0] for _ in range(args.rounds))
+            row["crop_kernel_us"], row["crop_kernel_us_rounds"], row["copy_us"], row["copy_eager_us"] = us, rounds_us, copy, copy_eager
+            row["ratio_to_copy"] = {k: v / copy[k.split("_", 1)[1]] for k, v in us.items()}
             res["rows"].append(row)
             emit()
             del ticks, det, surfs
