@@ -413,7 +413,10 @@ SY_API int sy_pack_weights(const sy_pack_entry* entries, int n_entries, int tota
  * nseg = 1 is an ordinary single-call BatchNorm.
  *
  * Training-mode BatchNorm helpers around sy_conv2d(stat_sum/stat_sqsum).
- * Replaces nn.BatchNorm2d in training mode (momentum/eps patched by init_yolo, cfgs/<name>.py:40-44). */
+ * Replaces nn.BatchNorm2d in training mode (momentum/eps patched by init_yolo, cfgs/<name>.py:40-44).
+ * sy_bn_finalize: every array is one of its own — scale / shift / mean / invstd / running_* overlap neither each other nor
+ * sum / sqsum / gamma / beta (the kernel takes them as __restrict__); above 64 rows, rows [0, 32) of sum / sqsum are overwritten
+ * with the folded totals. */
 SY_API int sy_bn_finalize(const float* sum, const float* sqsum, int C, int copies, double count, const float* gamma,
                    const float* beta, float eps, float momentum, float* running_mean,
                    float* running_var, float* scale, float* shift, float* mean, float* invstd,

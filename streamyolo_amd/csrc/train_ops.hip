@@ -333,6 +333,40 @@ __global__ __launch_bounds__(kSppTileThreads) void spp_pool_bwd_tile_kernel(type
 // by four partial sums (rows j = q mod 4 of that list) that are combined in order q — a fixed tree, so the result does not
 // depend on scheduling — with (C / 64) x kFoldTo workgroups instead of eight serial threads per channel.
 constexpr int kFoldTo = 32, kFoldAbove = 64;
+
+// A chain = the elements p[0], p[pitch], p[2 pitch], ... (n of them) added in index order onto +0.0f.  Sixteen loads are issued
+// before the sixteen dependent adds: one memory round trip per sixteen rows.  In the last round a row at or above n is not added,
+// and row k is loaded in its place: with a branch around each load instead, the compiler put an `s_waitcnt vmcnt(0)` into every
+// other branch (the 64-bit address product took the register pair of a load still in flight), eight serial round trips where
+// the source showed one.  These folds run a few workgroups wide on the step's frame chains: what they cost is the number of
+// dependent round trips, not the bytes.
+__device__ __forceinline__ float fold_chain(const float* p, long long pitch, int n) {
+    float acc = 0.0f;
+    int k = 0;
+    for (; k + 16 <= n; k += 16) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = p[(long long)(k + u) * pitch];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc += v[u];
+    }
+    if (k < n) {
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = p[(long long)(k + u < n ? k + u : k) * pitch];
+        sy_sched_fence();                               // (all sixteen loads before the first add's wait)
+#pragma unroll
+        for (int u = 0; u < 16; ++u)
+            if (k + u < n) acc += v[u];
+    }
+    return acc;
+}
+
+// Thread (cl, q) adds the rows j = q, q + 4, q + 8, ... of the class's list r, r + kFoldTo, ... (J rows): a chain of
+// n_q = ceil((J - q) / 4) rows, 4 kFoldTo rows apart, starting at row r + kFoldTo q.  fold_chain adds them in index order onto
+// +0.0f, which is what the loop this replaces did (acc = +0.0f, then acc += row j for j = q, q + 4, ... in order, four loads per
+// wait in its main loop and ONE per wait in its remainder): the same operands in the same order, so every bit of the four partial
+// sums and of their combination is the same, -0.0f rows included (a chain of no rows stays +0.0f in both).
 __global__ __launch_bounds__(kBlock) void fold_rows_kernel(float* a0, float* a1, int C, int copies) {
     __shared__ float part[4][64];
     float* const arr = (blockIdx.z & 1) ? a1 : a0;
@@ -341,26 +375,27 @@ __global__ __launch_bounds__(kBlock) void fold_rows_kernel(float* a0, float* a1,
     const int c = blockIdx.x * 64 + cl, r = blockIdx.y;
     float acc = 0.0f;
     if (c < C) {
-        int j = q;
         const int J = (copies - r + kFoldTo - 1) / kFoldTo;            // rows of this class
-        for (; j + 12 < J; j += 16) {                                 // four independent loads in flight, added in index order
-            const float v0 = base[(long long)(r + kFoldTo * j) * C + c], v1 = base[(long long)(r + kFoldTo * (j + 4)) * C + c];
-            const float v2 = base[(long long)(r + kFoldTo * (j + 8)) * C + c], v3 = base[(long long)(r + kFoldTo * (j + 12)) * C + c];
-            acc += v0; acc += v1; acc += v2; acc += v3;
-        }
-        for (; j < J; j += 4) acc += base[(long long)(r + kFoldTo * j) * C + c];
+        if (J > q) acc = fold_chain(base + (long long)(r + kFoldTo * q) * C + c, (long long)4 * kFoldTo * C, (J - q + 3) / 4);
     }
     part[q][cl] = acc;
     __syncthreads();
     if (q == 0 && c < C) base[(long long)r * C + c] = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
 }
 
-// `copies` rows are read, `stride` rows lie between the segments (stride > copies after fold_rows_kernel)
-__global__ __launch_bounds__(kBlock) void bn_finalize_kernel(const float* sum, const float* sqsum, int C, int copies, int stride,
-                                                             double count, const float* gamma, const float* beta,
-                                                             float eps, float momentum, float* running_mean,
-                                                             float* running_var, float* scale, float* shift,
-                                                             float* mean_out, float* invstd_out) {
+// `copies` rows are read, `stride` rows lie between the segments (stride > copies after fold_rows_kernel).
+// Every load of the launch is issued before its first wait: a thread's rows k = rg, rg + 8, ... (eight of them cover the 64 rows
+// the launcher ever passes; a row at or above `copies` is not added, row 0 is loaded in its place) and, in the rg == 0 threads, the channel's
+// gamma / beta / running statistics, which the old body loaded one by one after the barrier, each behind the store before it.
+// The additions, their operands and their order are unchanged.  The outputs are arrays of their own (__restrict__): no caller
+// passes a statistic or parameter array as an output.
+__global__ __launch_bounds__(kBlock) void bn_finalize_kernel(const float* __restrict__ sum, const float* __restrict__ sqsum, int C,
+                                                             int copies, int stride, double count,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             float eps, float momentum, float* __restrict__ running_mean,
+                                                             float* __restrict__ running_var, float* __restrict__ scale,
+                                                             float* __restrict__ shift, float* __restrict__ mean_out,
+                                                             float* __restrict__ invstd_out) {
     SY_TL_BEGIN(11);
     __shared__ float s_s[8][32], s_q[8][32];
     const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
@@ -372,8 +407,24 @@ __global__ __launch_bounds__(kBlock) void bn_finalize_kernel(const float* sum, c
         if (invstd_out != nullptr) invstd_out += ao;
     }
     float s = 0.0f, q = 0.0f;
-    if (c < C)
-        for (int k = rg; k < copies; k += 8) { s += sum[(long long)k * C + c]; q += sqsum[(long long)k * C + c]; }
+    float g = 0.0f, b = 0.0f, rm = 0.0f, rv = 0.0f;
+    if (c < C) {
+        float vs[8], vq[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int k = rg + 8 * u < copies ? rg + 8 * u : 0;      // (row 0 instead of a branch around the load: a predicated
+            vs[u] = sum[(long long)k * C + c];                        //  load takes its wait with it into the branch)
+            vq[u] = sqsum[(long long)k * C + c];
+        }
+        if (rg == 0) {
+            g = gamma[c]; b = beta[c];
+            if (running_mean != nullptr) { rm = running_mean[c]; rv = running_var[c]; }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (rg + 8 * u < copies) { s += vs[u]; q += vq[u]; }
+        for (int k = rg + 64; k < copies; k += 8) { s += sum[(long long)k * C + c]; q += sqsum[(long long)k * C + c]; }
+    }
     s_s[rg][cl] = s;
     s_q[rg][cl] = q;
     __syncthreads();
@@ -384,15 +435,15 @@ __global__ __launch_bounds__(kBlock) void bn_finalize_kernel(const float* sum, c
     double var = dq / count - mean * mean;
     if (var < 0.0) var = 0.0;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[c] * invstd;
+    const float sc = g * invstd;
     scale[c] = sc;
-    shift[c] = beta[c] - (float)mean * sc;
+    shift[c] = b - (float)mean * sc;
     if (mean_out != nullptr) mean_out[c] = (float)mean;
     if (invstd_out != nullptr) invstd_out[c] = invstd;
     if (running_mean != nullptr) {
         const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
-        running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)unbiased;
+        running_mean[c] = (1.0f - momentum) * rm + momentum * (float)mean;
+        running_var[c] = (1.0f - momentum) * rv + momentum * (float)unbiased;
     }
     SY_TL_END();
 }
@@ -706,6 +757,8 @@ __global__ __launch_bounds__(kBlock) void bn_silu_bwd_apply_kernel(const typenam
         }
     }
     if ((int)threadIdx.x >= rows * cpp) return;
+    // (loading these parameters above the fold and its barrier, next to the first rows, was measured in round 18: the kernel's
+    //  average in the step and the step itself did not move — profiles/r18 — so they stay here)
     float sc[T::kEPC], sh[T::kEPC], mu[T::kEPC], is[T::kEPC], gi[T::kEPC], m0[T::kEPC], m1[T::kEPC];
 #pragma unroll
     for (int j = 0; j < T::kEPC; ++j) {
@@ -769,30 +822,9 @@ __global__ __launch_bounds__(kBlock) void fold_replicas_kernel(float* sums, int 
 // A reduce launch writes only the first `live` = min(grid.x, copies) rows of a segment (sy_bn_bwd_reduce_live_rows); the rows
 // are sized for the reduce cap (768) and the rest stays +0.0f.  x + (+0.0f) == x for every x, and a live row is never -0.0f (it is
 // +0 + a from the atomic), so stopping a chain at its last live row leaves every bit of the result as fold_replicas_kernel
-// computes it.  A chain = the elements p[0], p[pitch], p[2 pitch], ... (n of them) added in index order onto +0.0f.  Sixteen
-// loads are issued before the sixteen dependent adds (fold_replicas_kernel waits for four at a time: one memory round trip per
-// four rows, 48 of them in a row at 768 rows and 2C / 64 workgroups).
-__device__ __forceinline__ float fold_chain(const float* p, long long pitch, int n) {
-    float acc = 0.0f;
-    int k = 0;
-    for (; k + 16 <= n; k += 16) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = p[(long long)(k + u) * pitch];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc += v[u];
-    }
-    if (k < n) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = (k + u < n) ? p[(long long)(k + u) * pitch] : 0.0f;
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-            if (k + u < n) acc += v[u];
-    }
-    return acc;
-}
-
+// computes it.  The chains are fold_chain's (above fold_rows_kernel): sixteen loads are issued before the sixteen dependent adds
+// (fold_replicas_kernel waits for four at a time: one memory round trip per four rows, 48 of them in a row at 768 rows and
+// 2C / 64 workgroups).
 // fold_replicas_kernel over rows [0, live) of segments `copies` rows apart (same grid, same tree: see fold_chain)
 __global__ __launch_bounds__(kBlock) void fold_replicas_live_kernel(float* sums, int n, int copies, int live) {
     __shared__ float part[4][64];
