@@ -812,6 +812,84 @@ SY_API int sy_crop_gather(const sy_crop_row* rows, int B, const float* boxes, in
                           const int32_t* cnt, int Ch, int Cw, int flags, int out_dtype, const float* mean3, const float* scale3,
                           void* out, int capacity, int32_t* out_index, int32_t* out_rect, int32_t* out_count, void* stream);
 
+/* ---- redacting a tick's boxes in camera surfaces: pixelate or fill what was detected, in place ----------------------------
+ * What sy_overlay_draw cannot do — outlines and tabs hide nothing: ONE launch makes the objects of every batch row's box list
+ * unrecognisable in that row's BGR / RGB / NV12 / P010 surface in DEVICE memory, from the device tensors the tick produced — no
+ * host read.  Geometry and style are per-row table data (sy_redact_row, DEVICE memory); the grid depends on (B, Hmax, Wmax)
+ * only, so one recorded launch serves any table and list contents.  Added to ABI 7 (nothing existing changed).
+ *
+ * boxes / layout / max_list / cnt: exactly as sy_overlay_draw (layout 0: det [B, max_list, 7], score = obj * class_conf in fp32;
+ * layout 1: [B, max_list, 6]).  Row b looks at its first
+ *     n = min(cnt[b], max_list)                                                              (cnt < 0 counts as 0)
+ * entries.  There is NO cap of 256: coverage is a union, the kernel walks the list in chunks of 256 (its LDS staging size) and
+ * ORs.  A redaction that drops entry 257 is a leak.
+ *
+ * The rule (all arithmetic on coordinates is fp32 IEEE without contraction up to the integer rectangle, 64-bit integers from
+ * there on):
+ * 1. Rectangle.  Rule 1 of sy_overlay_draw with the class filter of sy_crop_gather: with r(c) = floor(c / divisor + 0.5)
+ *    (clamped to +-2^30),  X1 = r(x1), Y1 = r(y1), X2 = r(x2) - 1, Y2 = r(y2) - 1, inclusive.  An entry is skipped when any c or
+ *    c / divisor + 0.5 is not finite, when X2 < X1 or Y2 < Y1, when its score is below min_score or NaN, when its class is NaN,
+ *    outside [0, 128) or (as an integer, truncated) has no bit in class_mask (bit c & 31 of word c >> 5).  All of this is
+ *    decided before padding and clipping: a box off the surface whose padding reaches into it is redacted there.
+ * 2. Padding.  Rule 2 of sy_crop_gather: with W = X2 - X1 + 1 and px = (W * pad_q8 + 128) >> 8:  X1 -= px, X2 += px; the same
+ *    in y with H.  (pad_q8 is clamped to 0..256.)
+ * 3. Shape.  SY_REDACT_RECT: every pixel of the padded rectangle is COVERED.  SY_REDACT_ELLIPSE: with the padded W and H, pixel
+ *    (x, y) of the rectangle is covered iff
+ *        ((2 x + 1) - (2 X1 + W))^2 H^2 + ((2 y + 1) - (2 Y1 + H))^2 W^2 <= W^2 H^2
+ *    — the pixel's centre lies inside the inscribed ellipse.  An entry whose W or H exceeds SY_REDACT_MAX_SIDE is covered as a
+ *    rectangle: the products stay inside 64 bits, and nothing is ever skipped for being large.
+ * 4. Union and clipping.  A pixel of [0, Ws) x [0, Hs) is covered iff any kept entry covers it; the result does not depend on
+ *    the order of the list.  (Hs <= Hmax and Ws <= Wmax is the caller's duty, as for sy_overlay_draw.)
+ * 5. SY_REDACT_FILL.  A covered pixel takes `fill`: BGR bytes 0..2, RGB the same bytes in the order R, G, B, luma byte 4.
+ * 6. SY_REDACT_PIXELATE.  Cells are aligned to the SURFACE's origin, not to the box: cell (i, j) is the pixels
+ *    x in [i cell, min((i + 1) cell, Ws) - 1], y in [j cell, min((j + 1) cell, Hs) - 1].  With n the cell's pixel count and S_c
+ *    the sum of the ORIGINAL values of channel c over the whole cell, covered or not, every covered pixel of the cell takes
+ *    (S_c + (n >> 1)) / n (integer division) in each channel.  A cell without a covered pixel is neither read nor written.
+ *    cell is 4, 8, 16 or 32; anything else makes the descriptor impossible (rule 9).
+ * 7. NV12 / P010.  Luma by rules 5 and 6.  A chroma sample is covered iff at least one of its four luma pixels is (rule 6 of
+ *    sy_overlay_draw).  FILL gives it (fill[5], fill[6]); PIXELATE averages U and V separately over the chroma samples of the
+ *    same cell — a (cell / 2) x (cell / 2) block clipped to the plane — with the same rounding.  P010 reads the HIGH byte of
+ *    every sample and writes v << 8 (bytes 0, v): the low bits of a redacted sample are gone too.
+ * 8. Untouched bytes.  Rule 7 of sy_overlay_draw, word for word: no byte the rule leaves uncovered is written at all —
+ *    uncovered pixels, the bytes between a row's payload and its pitch, padded luma rows, anything between the planes — and none
+ *    of those outside the payload is read.
+ * 9. Descriptors and status.  A descriptor no surface can have (the list of sy_overlay_draw: plane0 == NULL, Hs or Ws <= 0, an
+ *    unknown format, odd NV12 / P010 sizes, a pitch — either one — below the row's bytes, a negative chroma_stride; and here a
+ *    cell other than 4, 8, 16, 32, a mode or a shape outside 0..1) is skipped on the device, never written through.
+ *    SY_ERR_ARG for rows / boxes / cnt == NULL, B / max_list / Hmax / Wmax <= 0, a layout other than 0 or 1;
+ *    SY_ERR_UNSUPPORTED for B > 65535 or more than 65535 tile rows.
+ *
+ * Kernel shape: a gather.  A workgroup of 256 threads owns one SY_REDACT_TILE_H x SY_REDACT_TILE_W tile of one row's surface;
+ * both sides are multiples of the largest cell, so every cell lies in exactly one tile: a workgroup reads only pixels it owns,
+ * all of them before a barrier, and writes behind it — no workgroup reads a byte another one writes, which is what makes
+ * pixelation in place safe (a blur, whose window crosses tiles, would not be).  It compacts the entries that meet its tile chunk
+ * by chunk, leaves without touching pixel memory when none does, sums flagged cells with integer LDS adds (no order), then
+ * writes.  In the two-plane formats a thread owns 2 x 2 luma blocks with their chroma samples. */
+#define SY_REDACT_TILE_W 64         /* pixels: the tile of one workgroup; both sides multiples of 32                       */
+#define SY_REDACT_TILE_H 32
+#define SY_REDACT_MAX_SIDE 16384    /* an ellipse wider or taller than this is covered as its rectangle                    */
+#define SY_REDACT_PIXELATE 0        /* sy_redact_row::mode                                                                 */
+#define SY_REDACT_FILL 1
+#define SY_REDACT_RECT 0            /* sy_redact_row::shape                                                                */
+#define SY_REDACT_ELLIPSE 1
+typedef struct sy_redact_row {      /* 88 bytes, one per batch row, DEVICE memory                                          */
+    uint8_t* plane0;                /* BGR / RGB pixels or the luma plane; NULL or Hs == 0: nothing is redacted in this row */
+    uint8_t* plane1;                /* NV12 / P010 chroma plane; NULL: plane0 + row_stride * Hs.  Ignored for BGR / RGB    */
+    int32_t Hs, Ws, row_stride, chroma_stride;   /* as sy_frame_surf (chroma_stride 0 = row_stride)                        */
+    int32_t format;                 /* SY_PIX_BGR / RGB / NV12 / P010                                                      */
+    float divisor;                  /* box coordinate / divisor = surface pixel (detections: the row's in_scale; tracks: 1) */
+    float min_score;                /* entries with score < min_score (or NaN) are skipped                                 */
+    int32_t pad_q8;                 /* growth per side in 1/256 of the box side, 0..256 (clamped)                          */
+    int32_t mode;                   /* SY_REDACT_PIXELATE / SY_REDACT_FILL                                                 */
+    int32_t cell;                   /* pixelation cell in luma pixels: 4, 8, 16 or 32 (checked in both modes)              */
+    int32_t shape;                  /* SY_REDACT_RECT / SY_REDACT_ELLIPSE                                                  */
+    int32_t reserved;               /* 0 */
+    uint8_t fill[8];                /* B, G, R, 0, Y, U, V, 0: the fill colour in both spaces; the kernel converts nothing */
+    uint32_t class_mask[4];         /* as sy_det_policy: bit c & 31 of word c >> 5 set = class c is redacted               */
+} sy_redact_row;
+SY_API int sy_redact(const sy_redact_row* rows, int B, int Hmax, int Wmax, const float* boxes, int layout, int max_list,
+                     const int32_t* cnt, void* stream);
+
 /* backward of sy_resize_nearest (scatter-add into the source grid) */
 SY_API int sy_resize_nearest_bwd(const void* dout, int N, int Ho, int Wo, int C, int lddo, int64_t dobs,
                           void* din, int Hi, int Wi, int lddi, int64_t dibs, int accumulate,

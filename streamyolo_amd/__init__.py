@@ -17,10 +17,11 @@ from .streaming import MultiStreamDetector, StreamingDetector, TrackConfig
 from .scoring import DetectionScorer, score_coco
 from .overlay import OverlayStyle, draw_detections
 from .crops import CropSpec, Crops, crop_detections
+from .redact import RedactSpec, redact_detections
 
 __all__ = ["YOLOX", "DFPPAFPN", "TALHead", "PIPEHead", "CSPDarknet", "postprocess", "build_model", "DeviceGradScaler",
            "StreamingDetector", "MultiStreamDetector", "Surface", "TrackConfig", "DetectionPolicy", "DetectionScorer", "score_coco",
-           "OverlayStyle", "draw_detections", "CropSpec", "Crops", "crop_detections"]
+           "OverlayStyle", "draw_detections", "CropSpec", "Crops", "crop_detections", "RedactSpec", "redact_detections"]
 __version__ = "0.1.0"
 
 MODEL_ZOO = {

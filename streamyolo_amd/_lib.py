@@ -169,6 +169,21 @@ CROP_KEEP_ASPECT, CROP_RGB_OUT = 1, 2          # flags of sy_crop_gather
 CROP_DT_U8 = 3                                 # SY_CROP_DT_U8: out_dtype besides DT_BF16 / DT_F16 / DT_F32
 
 
+class RedactRow(C.Structure):
+    """sy_redact_row (include/streamyolo_hip.h): 88 bytes of DEVICE memory per batch row."""
+    _fields_ = [("plane0", C.c_void_p), ("plane1", C.c_void_p), ("Hs", C.c_int32), ("Ws", C.c_int32), ("row_stride", C.c_int32),
+                ("chroma_stride", C.c_int32), ("format", C.c_int32), ("divisor", C.c_float), ("min_score", C.c_float),
+                ("pad_q8", C.c_int32), ("mode", C.c_int32), ("cell", C.c_int32), ("shape", C.c_int32), ("reserved", C.c_int32),
+                ("fill", C.c_uint8 * 8), ("class_mask", C.c_uint32 * 4)]
+
+
+REDACT_TILE = (32, 64)                         # (SY_REDACT_TILE_H, SY_REDACT_TILE_W): the pixels one workgroup owns
+REDACT_MAX_SIDE = 16384                        # SY_REDACT_MAX_SIDE
+REDACT_PIXELATE, REDACT_FILL = 0, 1            # sy_redact_row.mode
+REDACT_RECT, REDACT_ELLIPSE = 0, 1             # sy_redact_row.shape
+REDACT_CELLS = (4, 8, 16, 32)                  # sy_redact_row.cell
+
+
 class ScoreParams(C.Structure):
     """sy_score_params (include/streamyolo_hip.h)."""
     _fields_ = [("n_thr", C.c_int32), ("n_rec", C.c_int32), ("n_area", C.c_int32), ("n_maxdet", C.c_int32),
@@ -249,6 +264,7 @@ SIGNATURES = {
     "sy_score_accumulate": (_I, [_P, _I, _I, C.POINTER(ScoreParams), _P, _P, _P, _P, _P]),
     "sy_overlay_draw": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "sy_crop_gather": (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "sy_redact": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "sy_splitk_epilogue": (_I, [_P, _I, _L, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "sy_rows_add_f32": (_I, [_P, _L, _P, _L, _I, _I, _I, _P]),
     "sy_pred_grad_fold_workspace_floats": (_L, [_I]),

@@ -592,6 +592,25 @@ def crop_gather(table, B, boxes, layout, ids, cnt, out, out_index, out_rect, out
           "sy_crop_gather")
 
 
+REDACT_TILE = _lib.REDACT_TILE                   # (rows, columns) of pixels one workgroup of sy_redact owns
+
+
+def redact(table, B, max_hw, boxes, layout, cnt):
+    """Pixelate or fill every batch row's box list in its surface, in place (sy_redact): `table` = uint8 device tensor holding B
+    sy_redact_row descriptors (88 bytes each: plane addresses, pitches, format, divisor, filters, padding, mode, cell, shape and
+    fill; redact.py fills and validates them), max_hw = (Hmax, Wmax) no row's surface exceeds.  layout 0: boxes fp32 [>= B, L, 7]
+    (sy_postprocess's det), layout 1: fp32 [>= B, L, 6] (sy_track_update's out).  cnt int32 [>= B].  Every one of a row's
+    min(cnt, L) entries is looked at.  One launch whose shape does not depend on the table or the lists."""
+    dev = table.device
+    assert table.dtype == torch.uint8 and table.is_contiguous() and table.numel() >= 88 * B and table.data_ptr() % 8 == 0
+    assert layout in (0, 1)
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and boxes.dim() == 3 and boxes.shape[2] == (6 if layout else 7)
+    assert boxes.shape[0] >= B and boxes.device == dev
+    assert cnt.dtype == torch.int32 and cnt.is_contiguous() and cnt.numel() >= B and cnt.device == dev
+    check(_lib.lib().sy_redact(table.data_ptr(), int(B), int(max_hw[0]), int(max_hw[1]), boxes.data_ptr(), int(layout),
+                               boxes.shape[1], cnt.data_ptr(), stream_of(table)), "sy_redact")
+
+
 def rows_add_f32(dst, src, rows, cols, ldd, lds, zero_src=False):
     """dst[r][:cols] += src[r][:cols] (fp32, row pitches ldd / lds in elements); zero_src: clear the source behind the read."""
     assert dst.dtype == torch.float32 and src.dtype == torch.float32

@@ -132,6 +132,7 @@ class StreamingDetector:
         self._last = None                                            # (det, cnt) of the latest frame (draw)
         self._overlay = self._style = None
         self._crop_rows, self._crop_spec, self._crop_out = None, None, None  # crops(): the sy_crop_row table, the default spec, crops.CropCache
+        self._redact_rows = self._redact_spec = None                 # redact(): the sy_redact_row table, the default spec
         self._post = lambda out: postprocess_device(out, num_classes, conf_thre, nms_thresh)   # one object: part of the tape key
         if row is not None:
             # a DetectionPolicy (class list, class-agnostic NMS, caps): the post step is sy_postprocess_rows over a one-row table
@@ -187,6 +188,25 @@ class StreamingDetector:
         self._overlay.set_row(0, target, self.in_scale, style)
         self._overlay.upload()
         draw_rows(self._overlay, self.frame_hw, det, 0, None, cnt, style)
+        return surface
+
+    def redact(self, surface, spec=None):
+        """Pixelate or fill the latest frame's detections in `surface` (a data.Surface, or a uint8 device tensor [H, W, 3] taken
+        as BGR, of the camera's size), in place, and return it: MultiStreamDetector.redact over this detector's one row.  IN
+        PLACE — redact a `clone()` while the decoder may still hold the surface as a reference frame; redact() before draw()."""
+        from .redact import RedactRows, RedactSpec, as_target, check_spec, redact_rows
+        if spec is None:
+            spec = self._redact_spec = self._redact_spec or RedactSpec()
+        check_spec(spec, "StreamingDetector")
+        if self._last is None:
+            raise ValueError("StreamingDetector: no frame has been detected yet")
+        det, cnt = self._last
+        target = as_target(surface, det.device, self.frame_hw, "StreamingDetector")
+        if self._redact_rows is None:
+            self._redact_rows = RedactRows(1, det.device)
+        self._redact_rows.set_row(0, target, self.in_scale, spec)
+        self._redact_rows.upload()
+        redact_rows(self._redact_rows, self.frame_hw, det, 0, cnt)
         return surface
 
     def crops(self, surface, spec=None):
@@ -355,6 +375,7 @@ class MultiStreamDetector:
         self._last = None                                        # (det, cnt) of the latest tick
         self._overlay = self._style = None                       # draw(): the sy_overlay_row table, the default style
         self._crop_rows, self._crop_spec, self._crop_out = None, None, None  # crops(): the sy_crop_row table, the default spec, crops.CropCache
+        self._redact_rows = self._redact_spec = None                 # redact(): the sy_redact_row table, the default spec
 
     # ---- stream bookkeeping (host side only) --------------------------------------------------------------------
     def _policy_record(self, policy):
@@ -632,6 +653,49 @@ class MultiStreamDetector:
             draw_rows(self._overlay, max_hw, self.tracks.out, 1, self.tracks.out_id, self.tracks.out_cnt, style)
         else:
             draw_rows(self._overlay, max_hw, self._last[0], 0, None, self._last[1], style)
+        return surfaces
+
+    def redact(self, surfaces, sids, spec=None):
+        """Pixelate or fill the latest tick's results of the streams `sids` in `surfaces`, in place, and return them (redact.py;
+        the rule: include/streamyolo_hip.h).  A target is what draw() takes: a data.Surface (bgr / rgb / nv12 / p010) or a uint8
+        device tensor [H, W, 3] taken as BGR, of the stream's camera size, on the detector's device.  Redaction is IN PLACE: a
+        decoder surface still held as a reference frame must NOT be redacted — pass `[s.clone() for s in ...]`.  With tracking
+        the tracker's forecast output is redacted (camera coordinates; a track survives a missed detection, so the object stays
+        hidden through a flickered frame), without it the detections (divided by the stream's box divisor).  Every list entry is
+        looked at: no cap.  spec: a redact.RedactSpec (None: the defaults).  Order: redact() BEFORE draw(), so that the drawing
+        lies on top of the pixelated boxes and stays legible.  ONE launch on the current stream behind the tick, its table one
+        non-blocking copy from pinned memory: no host read, no synchronisation, and not on the tick's tape.  ValueError — before
+        anything is written — for a stream without a frame in the latest tick, a stream named twice, a target on another
+        device or of another size."""
+        from .redact import RedactRows, RedactSpec, as_target, check_spec, redact_rows
+        surfaces, sids = list(surfaces), list(sids)
+        if len(surfaces) != len(sids):
+            raise ValueError("MultiStreamDetector: %d targets for %d stream ids" % (len(surfaces), len(sids)))
+        if spec is None:
+            spec = self._redact_spec = self._redact_spec or RedactSpec()
+        check_spec(spec, "MultiStreamDetector")
+        if len(set(sids)) != len(sids):
+            raise ValueError("MultiStreamDetector: a stream id appears twice in one redact: %r" % (sids,))
+        targets = []
+        for t, sid in zip(surfaces, sids):
+            self._known(sid)
+            if sid not in self._row_of:
+                raise ValueError("MultiStreamDetector: stream %r had no frame in the latest tick" % (sid,))
+            targets.append(as_target(t, self.device if self._last is None else self._last[0].device, self._geom[sid][0],
+                                     "MultiStreamDetector"))
+        if not sids:
+            return surfaces
+        if self._redact_rows is None:
+            self._redact_rows = RedactRows(self.batch, self._last[0].device)
+        self._redact_rows.clear()
+        for t, sid in zip(targets, sids):
+            self._redact_rows.set_row(self._row_of[sid], t, 1.0 if self.tracks is not None else self._geom[sid][2], spec)
+        self._redact_rows.upload()
+        max_hw = self.max_frame_hw or self.frame_hw
+        if self.tracks is not None:
+            redact_rows(self._redact_rows, max_hw, self.tracks.out, 1, self.tracks.out_cnt)
+        else:
+            redact_rows(self._redact_rows, max_hw, self._last[0], 0, self._last[1])
         return surfaces
 
     def crops(self, surfaces, sids, spec=None):

@@ -85,6 +85,16 @@ of a tensor the size of the crops written, the bytes any method must store — t
 launch tape); `copy_eager_us`: torch's copy_ of the same tensor issued eagerly.
 
     python tools/multistream_probe.py --crops 1 --batches 1,8
+
+--redact 1: pixelating the tick's boxes in the camera frames on the device (MultiStreamDetector.redact, sy_redact; not on the
+tape), three things in one process, alternating.  `tick_ms_per_tick` / `tick_redact_ms_per_tick`: the tick alone and with one
+redact() of every row's BGR frame behind it (pixelate, cell 16, pad 0.1, min_score 0.01; `boxes_redacted_per_row`), per-round
+times and `redact_ms_per_tick` (best minus best, to be read against the spread).  `redact_kernel_us`: the launch alone on B
+1200x1920 BGR and NV12 surfaces, PIXELATE cell 16 and FILL, with 30 and with 256 boxes per row (the grids of --overlay 1), --ticks
+launches replayed back to back from a launch tape between two events (the launch gaps included).  `clone_us`: the yardstick — a
+plain device copy of the same B surfaces (Surface.clone()), timed in the same run.
+
+    python tools/multistream_probe.py --redact 1 --batches 1,8
 """
 import argparse
 import json
@@ -124,6 +134,7 @@ def main():
     ap.add_argument("--policy", type=int, default=0, help="1: the tick through sy_postprocess_rows (default and capped rows) beside today's")
     ap.add_argument("--overlay", type=int, default=0, help="1: the tick with and without draw(), the overlay launch alone, Surface.clone()")
     ap.add_argument("--crops", type=int, default=0, help="1: the tick with and without crops(), the crop call alone, a copy of the crops' bytes")
+    ap.add_argument("--redact", type=int, default=0, help="1: the tick with and without redact(), the redact launch alone, Surface.clone()")
     ap.add_argument("--tree", default=None, help="root of another checkout of the repository to import the package from")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -378,6 +389,76 @@ def main():
                 [sf.clone() for sf in ss]
                 clone[name] = 1e3 * min(timed(lambda: [sf.clone() for sf in ss], args.ticks)[0] for _ in range(args.rounds))
             row["overlay_kernel_us"], row["clone_us"] = us, clone
+            res["rows"].append(row)
+            emit()
+            del ticks, det, surfs
+        print(emit())
+        return
+
+    if args.redact:
+        if args.mixed or args.surfaces or args.track or args.score or args.policy or args.overlay or args.crops or fmt != "bgr":
+            ap.error("--redact is a separate measurement")
+        from streamyolo_amd import ops
+        from streamyolo_amd.data import Surface
+        from streamyolo_amd.redact import RedactRows, RedactSpec
+        from streamyolo_amd.streaming import MultiStreamDetector
+        res.update({"redact": True})
+        tick_spec = RedactSpec(mode="pixelate", cell=16, pad=0.1, min_score=0.01)
+        for B in batches:
+            det = MultiStreamDetector(model, hw, max_streams=max(B, 2), batch=B, dtype=args.dtype, device=dev)
+            det.warm_up(args.warmup)
+            sids = [det.open() for _ in range(B)]
+            canvases = [f.clone() for f in frames[:B]]           # redacted again and again: the cost does not depend on what is there
+
+            def tick_redact():
+                det.detect_device(frames[:B], sids)
+                det.redact(canvases, sids, tick_spec)
+            ticks = {"tick": lambda: det.detect_device(frames[:B], sids), "tick_redact": tick_redact}
+            rounds = {k: [] for k in ticks}
+            for _ in range(args.rounds):                         # alternate: clocks and neighbours drift between rounds
+                for k, fn in ticks.items():
+                    fn()
+                    rounds[k].append(timed(fn, args.ticks)[0])
+            row = {"batch": B, "active": B}
+            for k, v in rounds.items():
+                row.update({k + "_ms_per_tick": min(v), k + "_ms_rounds": v, k + "_spread_ms": max(v) - min(v)})
+            row["redact_ms_per_tick"] = min(rounds["tick_redact"]) - min(rounds["tick"])
+            r = det.detect_device(frames[:B], sids)
+            L = r[0].shape[1]
+            score = (r[0][:B, :, 4] * r[0][:B, :, 5] >= 0.01) & (torch.arange(L, device=dev)[None] < r[1][:B, None])
+            row["boxes_redacted_per_row"] = score.sum(dim=1).cpu().tolist()
+            # the launch alone, and the copy it stands against
+            nv12 = [bgr_to_nv12(f) for f in frames[:B]]
+            surfs = {"bgr": [Surface(f.clone(), "bgr") for f in frames[:B]],
+                     "nv12": [Surface((f[:hw[0]], f[hw[0]:]), "nv12") for f in nv12]}
+            us, clone = {}, {}
+            for name, ss in surfs.items():
+                for mode in ("pixelate", "fill"):
+                    table = RedactRows(B, dev)
+                    for b, sf in enumerate(ss):
+                        table.set_row(b, sf, 1.0, RedactSpec(mode=mode, cell=16, pad=0.0, fill=(40, 40, 40)))
+                    table.upload()
+                    for k, (gw, bw, bh) in ((30, (6, 150, 100)), (256, (32, 56, 36))):       # (the boxes of --overlay 1)
+                        g = torch.arange(256, device=dev, dtype=torch.float32)
+                        x1, y1 = (g % gw) * (hw[1] // gw) + 8, (g // gw) * (hw[0] // -(-256 // gw) if k == 256 else hw[0] // 5) + 40
+                        box = torch.stack([x1, y1, x1 + bw, y1 + bh, 1.0 - g / 512, g % 8], dim=1)
+                        lists = box[None].repeat(B, 1, 1).contiguous()
+                        cnt_k = torch.full((B,), k, dtype=torch.int32, device=dev)
+
+                        def kernel():
+                            ops.redact(table.table, B, hw, lists, 1, cnt_k)
+                        kernel()
+                        tape = _lib.NativeTape()
+                        with tape:
+                            for _ in range(args.ticks):
+                                kernel()
+                        stream = ops.stream_of(lists)
+                        tape.replay(stream, None)
+                        us["%s_%s_%d" % (name, mode, k)] = \
+                            1e3 * min(timed(lambda: tape.replay(stream, None), 3)[0] for _ in range(args.rounds)) / args.ticks
+                [sf.clone() for sf in ss]
+                clone[name] = 1e3 * min(timed(lambda: [sf.clone() for sf in ss], args.ticks)[0] for _ in range(args.rounds))
+            row["redact_kernel_us"], row["clone_us"] = us, clone
             res["rows"].append(row)
             emit()
             del ticks, det, surfs
